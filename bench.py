@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — image-pairs/sec of the SuperPoint+SuperGlue hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`)
 
 A "step" is one pass of the hot path over one batch of synthetic pairs already resident in HBM:
@@ -11,7 +11,16 @@ world > 1 — by the one collective of the path, an RCCL gather of the fixed-siz
 Workload = BASELINE.json configs[2]/[3] shape ("C3"): 640x480 grayscale, d=128, 1024 keypoints,
 30 Sinkhorn iterations, synthetic BN-calibrated weights (no trained weights exist: LFS pointers).
 
-Rank 0 prints ONE JSON line (contract in the task statement) including
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0): metric, value, unit, higher_is_better,
+dtype, ms_per_step (wall-clock milliseconds of one timed step), "step_ms" (min / median / max of the K timed steps, HIP
+events around each step), the config and, at N > 1, "compute_ms_per_step" / "gather_ms_per_step" (HIP events either side
+of the collective, max over ranks), "backend" = what the process group really runs on, and "world_checked".
+--dump-outputs DIR writes what the LAST timed step computed (the arrays a caller of the path receives) as DIR/<name>.npy,
+float32 (float64 for integer arrays), at most 64 MB in all: an array that would not fit is stored as a fixed, seeded sample
+of its flattened elements.  The inputs and weights are seeded, so two builds compare output for output.
+
+--full adds everything else the benchmark measures or checks, after the timed steps (and a clock sampler inside them);
+--no-cpu-baseline / --no-roofline-pass / --no-extras drop parts of it.  With --full rank 0's line also holds
   "roofline":     the dominant kernel against the gfx950 peak, from per-launch HIP events on the launch stream
                   over a second, instrumented pass of the same K steps.  `achieved`/`frac` are the rate the
                   matrix cores actually EXECUTE (never above 1); where a kernel executes fewer multiplies than
@@ -30,12 +39,10 @@ Rank 0 prints ONE JSON line (contract in the task statement) including
                   the reference's committed outputs on it (tests/golden/strict_c3.npz): keypoint sets and match indices
                   identical (exact ties of the reference's own Z and scores within 1e-4 of the threshold excepted, counted),
                   matching scores and samples of gnn17 / scores_in / Z against the north_star tolerance;
-  "step_ms":      min / median / max of the K timed steps (HIP events around each step), "clocks": sclk / socket power sampled
-                  from sysfs during the timed region, "roofline.frac_at_clock": the fraction against the peak at that clock;
+  "clocks":       sclk / socket power sampled from sysfs during the timed region, "roofline.frac_at_clock": the fraction against
+                  the peak at that clock;
   "c2":           SuperPoint-only images/s (BASELINE configs[1]) on the same resident images;
   "c5":           a short leg on the stress configuration (BASELINE configs[4]) with its own parity_in_run;
-  N > 1 lines:    "compute_ms_per_step" / "gather_ms_per_step" (HIP events either side of the collective, max over ranks),
-                  "backend" = what the process group really runs on, "world_checked";
   "gather_ms":    the path's one collective (RCCL gather of the step's match records) timed at world 1 as the N>1 baseline;
   "latency_b1_ms":          Matching.forward on ONE pair (BASELINE configs[2]), median of 50 synchronised calls;
   "pcie_inclusive_pairs_s": the same step fed from uint8 frames in pinned host memory (never `value`);
@@ -369,6 +376,36 @@ def log(msg):
         print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6
+NPY_HEADER_BYTES = 256          # room left per file for the .npy header (128 bytes for these shapes)
+
+
+def dump_outputs(arrays, out_dir, limit=DUMP_LIMIT_BYTES, seed=0):
+    """Writes `arrays` (name -> tensor or array) as out_dir/<name>.npy: floating arrays as float32, integer and bool arrays as
+    float64 (exact).  When the files would exceed `limit` bytes, the budget is shared out from the smallest array up, and an array
+    larger than its share is replaced by a sample of its flattened elements at fixed positions (a generator seeded with `seed`
+    and the array's size: equal shapes give equal positions in every run).  Returns {name: {"shape", "sampled"}}."""
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        host[name] = a.astype(np.float32 if np.issubdtype(a.dtype, np.floating) else np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    left, meta = limit - NPY_HEADER_BYTES * len(host), {}
+    order = sorted(host, key=lambda n: host[n].nbytes)
+    for i, name in enumerate(order):
+        a = host[name]
+        share = left // (len(order) - i)
+        sampled = None
+        if a.nbytes > share:
+            sampled = max(1, share // a.itemsize)
+            pos = np.sort(np.random.default_rng([seed, a.size]).choice(a.size, sampled, replace=False))
+            a = a.reshape(-1)[pos]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+        meta[name] = {"shape": list(host[name].shape), "sampled": sampled}
+    return meta
+
+
 def resident_inputs(wl, pair_ids, device):
     """This rank's pairs of the global batch, resident in HBM: pair i of the job = synth_pair(seed0 + i)."""
     ims = [synth.synth_pair(wl["seed0"] + pid, wl["H"], wl["W"]) for pid in pair_ids]
@@ -664,9 +701,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--pairs-per-gpu", type=int, default=64, help="pairs per step per GPU (weak scaling)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c3")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline-pass", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip latency_b1_ms / pcie_inclusive_pairs_s / c5 / gather_ms")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beyond the headline: clocks, parity_in_run(_strict), "
+                         "roofline pass, latency_b1_ms / pcie_inclusive_pairs_s / gather_ms / c2 / c5, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-roofline-pass", action="store_true", help="with --full: skip the roofline pass")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip parity_in_run_strict / latency_b1_ms / pcie_inclusive_pairs_s / c2 / c5 / gather_ms")
     ap.add_argument("--cpu-baseline-worker", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--plan-only", action="store_true", help="print this rank's share of the job (pair ids, record rows) as JSON and exit; no GPU needed")
     args = ap.parse_args()
@@ -733,7 +775,8 @@ def main():
             kp, sc, ds, cnt = eng.superpoint_batch(img01)
             if mid is not None:
                 mid.record()
-            return {"counts0": cnt[:B], "counts1": cnt[B:], "matches0": cnt.new_zeros(1) + 1}, torch.zeros(world * B, 1)
+            return {"keypoints": kp, "scores": sc, "descriptors": ds, "counts": cnt,
+                    "counts0": cnt[:B], "counts1": cnt[B:], "matches0": cnt.new_zeros(1) + 1}, torch.zeros(world * B, 1)
         out = matching.match_batch(img0, img1)
         rec = matching.pack_records(pair_ids_dev, out, pad_to=rows_per_rank)     # one kernel (imx_pack_records)
         if mid is not None:
@@ -745,14 +788,15 @@ def main():
         if use_pg:
             dist.barrier()
 
-    sampler = ClockSampler(device)
+    sampler = ClockSampler(device) if args.full else None
     stats = {}
 
     def timed(n):
         ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(n)]      # step start | before the collective | step end
         barrier()
         torch.cuda.synchronize()
-        sampler.start()
+        if sampler:
+            sampler.start()
         t0 = time.perf_counter()
         for i in range(n):
             ev[i][0].record()
@@ -761,7 +805,8 @@ def main():
         torch.cuda.synchronize()
         barrier()
         dt = time.perf_counter() - t0
-        sampler.stop()
+        if sampler:
+            sampler.stop()
         per = np.array([e[0].elapsed_time(e[2]) for e in ev])
         comp = float(np.mean([e[0].elapsed_time(e[1]) for e in ev]))
         gath = float(np.mean([e[1].elapsed_time(e[2]) for e in ev]))
@@ -782,20 +827,33 @@ def main():
     dt, out, rec = timed(args.steps)
     log(f"timed region done: {dt:.3f}s for {args.steps} steps")
 
-    # harness checks: every image yields exactly K keypoints; the gather holds every pair once
+    # every image yields exactly K keypoints
     c0, c1 = out["counts0"].cpu().numpy(), out["counts1"].cpu().numpy()
     assert (c0 == K).all() and (c1 == K).all(), f"keypoint counts != {K}: {c0} {c1}"
-    if not sp_only and rank == 0:
+    n_matches = int((out["matches0"] > -1).sum().item())
+    assert n_matches > 0
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from the last step: the match_pairs tensors of this rank's pairs (SuperPoint's
+        # tensors at C2) and, when a process group runs, the gathered records of every rank's pairs
+        if sp_only:
+            arrays = {k: out[k] for k in ("keypoints", "scores", "descriptors", "counts")}
+        else:
+            arrays = dict(out)
+            if use_pg:
+                arrays.update({"gathered_" + k: v for k, v in shard.unpack_records(rec).items()})
+        dumped = dump_outputs(arrays, args.dump_outputs)
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
+    # harness checks (--full): the gather holds every pair once
+    if args.full and not sp_only and rank == 0:
         assert rec.shape == (world * B, shard.record_width(K))
         assert sorted(shard.pair_ids_of(rec).cpu().tolist()) == list(range(world * B))
         if world == 1:
             assert torch.equal(rec, shard.pack_records(pair_ids, out)), "imx_pack_records differs from the host statement of the record layout"
-    n_matches = int((out["matches0"] > -1).sum().item())
-    assert n_matches > 0
     # parity of what was just timed: this rank's sweep-seed pairs of the LAST timed step against the reference's committed outputs
-    parity = parity_in_run(wl, pair_ids, out) if (not sp_only and rank == 0) else None
+    parity = parity_in_run(wl, pair_ids, out) if (args.full and not sp_only and rank == 0) else None
     strict = None
-    if not sp_only and rank == 0 and wl["sweep"] and not args.no_extras:
+    if args.full and not sp_only and rank == 0 and wl["sweep"] and not args.no_extras:
         log("parity_in_run_strict: the same pairs with the 't' SuperGlue weight set (untimed)")
         strict = parity_in_run_strict(matching, wl, pair_ids, img0, img1, sd_sg)
 
@@ -815,20 +873,23 @@ def main():
                    "weights": "synthetic, BN-calibrated (synth.py seeds 123/456)", "matches_per_pair": round(n_matches / B, 1),
                    "inputs": f"synth_pair(seed = {wl['seed0']} + pair index): the first pairs are the unselected sweep seeds of the parity tests"},
     }
+    if dumped is not None:
+        line["outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     if parity is not None:
         line["parity_in_run"] = parity
     if strict is not None:
         line["parity_in_run_strict"] = strict
     line["step_ms"] = stats["step_ms"]
-    line["clocks"] = sampler.report()
-    # the box beside the number: boxes of this pool differ by +-4 % in sustained clock under this power-bound step, as
-    # much as a round's gain; `value` is what was measured, `value_at_2400MHz` the same scaled to the clock the peaks are quoted at
-    _clk = (line["clocks"].get("sclk_mhz") or {}).get("median")
-    line["sclk_mhz_median"] = _clk
-    line["socket_power_w_median"] = (line["clocks"].get("socket_power_w") or {}).get("median")
-    line["value_at_2400MHz"] = round(value * 2400.0 / _clk, 3) if _clk else None
-    line["value_at_2400MHz_note"] = ("value x 2400 / median sclk of rank 0's GPU inside the timed region: a normalisation for comparing runs on "
-                                     "different boxes, not a measurement (HBM-bound kernels do not scale with sclk)")
+    if sampler:
+        line["clocks"] = sampler.report()
+        # the box beside the number: boxes of this pool differ by +-4 % in sustained clock under this power-bound step, as
+        # much as a round's gain; `value` is what was measured, `value_at_2400MHz` the same scaled to the clock the peaks are quoted at
+        _clk = (line["clocks"].get("sclk_mhz") or {}).get("median")
+        line["sclk_mhz_median"] = _clk
+        line["socket_power_w_median"] = (line["clocks"].get("socket_power_w") or {}).get("median")
+        line["value_at_2400MHz"] = round(value * 2400.0 / _clk, 3) if _clk else None
+        line["value_at_2400MHz_note"] = ("value x 2400 / median sclk of rank 0's GPU inside the timed region: a normalisation for comparing runs on "
+                                         "different boxes, not a measurement (HBM-bound kernels do not scale with sclk)")
     if use_pg:
         line["backend"] = {"process_group": dist.get_backend(), "collective": "RCCL gather (ncclSend/ncclRecv group) over xGMI" if backend == "nccl" else f"{backend} on the host (bring-up hook)"}
         line["world_checked"] = {"WORLD_SIZE": world, "--gpus": args.gpus, "process_group_size": dist.get_world_size(), "ranks_counted_by_all_reduce": world}
@@ -840,7 +901,7 @@ def main():
     # (every rank runs the steps -- step() contains the gather, a rank-0-only pass would hang the others;
     #  only rank 0 records events and reports)
     rows = None
-    if not args.no_roofline_pass:
+    if args.full and not args.no_roofline_pass:
         eng = matching._shared.engine
         if rank == 0:
             log("roofline pass (per-launch HIP events)")
@@ -859,8 +920,9 @@ def main():
         if clk and line["roofline"]["bound"] == "mfma":
             line["roofline"]["frac_at_clock"] = round(line["roofline"]["frac"] * 2400.0 / clk, 4)
             line["roofline"]["frac_at_clock_note"] = f"frac x 2400 / {clk} MHz: the peak is quoted at 2.4 GHz, the median sclk sampled inside the timed region was {clk} MHz"
-    line["config"]["arithmetic"] = arithmetic_text(line.get("roofline"))
-    if rank == 0 and world == 1 and not sp_only and not args.no_extras:
+    if args.full:
+        line["config"]["arithmetic"] = arithmetic_text(line.get("roofline"))
+    if args.full and rank == 0 and world == 1 and not sp_only and not args.no_extras:
         log("single-pair latency (Matching.forward, B = 1)")
         line["latency_b1_ms"] = latency_b1(matching, wl, device)
         log("PCIe-inclusive rate (IngestPipeline)")
@@ -877,7 +939,7 @@ def main():
             line["c5"] = c5_leg(device)
     if use_pg:
         barrier()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not sp_only:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not sp_only:
         log("cpu baseline (oracle on host cores)")
         line["cpu_baseline"] = cpu_baseline(args.workload)
     if rank == 0:

@@ -244,7 +244,7 @@ def test_bench_through_the_driver_launch_line_with_rccl():
     env = dict(os.environ, IMX_BENCH_FORCE_PG="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29533", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--pairs-per-gpu", "4", "--no-cpu-baseline", "--no-extras"]
+           "--pairs-per-gpu", "4", "--full", "--no-cpu-baseline", "--no-extras"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -256,8 +256,8 @@ def test_bench_through_the_driver_launch_line_with_rccl():
     assert line["roofline"]["kernels"]["qkv_proj"]["form"] in ("gemm_h2:f16x2", "gemm_x3:bf16x3", "gemm_small:f32")
 
 
-def test_bench_default_invocation_prints_exactly_one_line():
-    """`python bench.py` as the driver runs it at N = 1 (extras on: the world-1 RCCL gather initialises a communicator, whose
+def test_bench_full_invocation_prints_exactly_one_line():
+    """`python bench.py --full` at N = 1 (extras on: the world-1 RCCL gather initialises a communicator, whose
     version banner RCCL writes to the C stdout): stdout must hold the JSON line and nothing else."""
     import json
     import os
@@ -265,7 +265,7 @@ def test_bench_default_invocation_prints_exactly_one_line():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--pairs-per-gpu", "4", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--pairs-per-gpu", "4", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -275,6 +275,44 @@ def test_bench_default_invocation_prints_exactly_one_line():
                 "data", "config", "roofline", "latency_b1_ms", "gather_ms", "c5"):
         assert key in line, key
     assert line["gather_ms"] is not None, line.get("gather_note")
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_timed_step(tmp_path):
+    """`python bench.py --steps K --warmup W` as the driver runs it, with --dump-outputs: one JSON line holding the headline and
+    nothing that needs runs of its own (no roofline pass, extras, parity or CPU baseline), `steps` as asked, and the last timed
+    step's arrays on disk -- float32 / float64, shaped as match_pairs returns them, and equal (keypoint sets, matches) to the
+    reference's committed outputs on the sweep seeds the first pairs are."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    B, K, dump = 4, 1024, tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--pairs-per-gpu", str(B),
+           "--dump-outputs", str(dump)]
+    r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "step_ms"):
+        assert key in line, key
+    assert line["steps"] == 3 and line["unit"] == "image-pairs/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["value"] > 0 and abs(line["value"] * line["ms_per_step"] / 1e3 - B) < 1e-2 * B
+    for key in ("roofline", "parity_in_run", "parity_in_run_strict", "clocks", "latency_b1_ms", "gather_ms", "c2", "c5", "cpu_baseline"):
+        assert key not in line, key
+    want = {"keypoints0": (B, K, 2), "keypoints1": (B, K, 2), "scores0": (B, K), "scores1": (B, K), "counts0": (B,), "counts1": (B,),
+            "matches0": (B, K), "matches1": (B, K), "matching_scores0": (B, K), "matching_scores1": (B, K)}
+    assert sorted(os.listdir(dump)) == sorted(k + ".npy" for k in want)
+    a = {k: np.load(dump / (k + ".npy")) for k in want}
+    for k, shape in want.items():
+        assert a[k].shape == shape and a[k].dtype in (np.float32, np.float64), (k, a[k].shape, a[k].dtype)
+    assert (a["counts0"] == K).all() and (a["counts1"] == K).all()
+    g = util.golden("sweep_c3.npz")
+    for b in range(B):                # pair b of the job is sweep seed index b (seed0 = 1000)
+        res = util.sweep_compare_end_to_end(g, b, a["keypoints0"][b], a["keypoints1"][b], a["matches0"][b].astype(np.int64))
+        assert not res["unexplained"] and not res["kp_bad"], (b, res)
 
 
 @pytest.mark.parametrize("seed", util.fuzz_seeds([0, 1, 2, 3, 4, 5, 6, 7]))

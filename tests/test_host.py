@@ -301,6 +301,35 @@ def test_bench_plans_the_c4_job_without_a_gpu():
     assert bad.returncode != 0 and "WORLD_SIZE=8" in (bad.stderr + bad.stdout)
 
 
+def test_bench_dump_outputs_float_arrays_within_the_byte_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs writes through dump_outputs(): floating arrays as float32, integer arrays as float64 (exact); over
+    the byte budget an array larger than its share is replaced by a sample at fixed, seeded positions (the same in every run),
+    the smaller arrays stay whole and the files together fit the budget."""
+    import importlib
+    # bench.py sets a default for this variable at import: keep the test process's environment as it was
+    monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
+    bench = importlib.import_module("bench")
+    rng = np.random.RandomState(0)
+    arrays = {"keypoints0": torch.from_numpy(rng.rand(4, 50, 2).astype(np.float32)), "matches0": torch.arange(200).reshape(4, 50) - 1,
+              "counts0": np.array([50, 50, 49, 50], np.int32), "descriptors0": rng.rand(100000)}
+    limit = 200000
+    metas = [bench.dump_outputs(arrays, str(tmp_path / run), limit=limit) for run in ("a", "b")]
+    assert metas[0] == metas[1]
+    files = {run: {k: np.load(tmp_path / run / (k + ".npy")) for k in arrays} for run in ("a", "b")}
+    a = files["a"]
+    assert sum(os.path.getsize(tmp_path / "a" / (k + ".npy")) for k in arrays) <= limit
+    assert a["keypoints0"].dtype == np.float32 and np.array_equal(a["keypoints0"], arrays["keypoints0"].numpy())
+    assert a["matches0"].dtype == np.float64 and np.array_equal(a["matches0"], arrays["matches0"].numpy())
+    assert a["counts0"].dtype == np.float64 and np.array_equal(a["counts0"], arrays["counts0"])
+    d = a["descriptors0"]
+    assert d.dtype == np.float32 and d.ndim == 1 and 0 < d.size < 100000 and metas[0]["descriptors0"] == {"shape": [100000], "sampled": d.size}
+    assert np.isin(d, arrays["descriptors0"].astype(np.float32)).all()
+    for k in arrays:                  # a second run writes the same files, sample positions included
+        assert np.array_equal(files["b"][k], a[k]), k
+    whole = bench.dump_outputs(arrays, str(tmp_path / "c"))          # the default budget (64 MB) holds these whole
+    assert all(m["sampled"] is None for m in whole.values())
+
+
 def test_package_and_library_versions_agree():
     import image_matching_amd
     from image_matching_amd import _lib

@@ -55,7 +55,18 @@ def test_superglue_dense_and_matches():
     util.assert_close(dn["gnn_taps"][0][0], g["tap0_0"], "gnn layer 0", atol=1e-5, rtol=1e-5)
     util.assert_close(dn["gnn_taps"][1][1], g["tap1_1"], "gnn layer 1", atol=1e-5, rtol=1e-5)
     util.assert_close(dn["gnn0"], g["gnn0"], "gnn out", atol=1e-4, rtol=1e-5)
-    util.assert_close(dn["scores_in"], g["scores_in"], "scores_in", atol=1e-4, rtol=1e-5)
+    # scores_in sums 128 products of features 18 layers deep: the reference's own fp32 result sits up to 0.7 of this tolerance from its
+    # float64 evaluation (fp64_anchor.npz), so fp32 evaluations on hosts whose CPU kernels sum in another order (another ISA, thread
+    # count or vendor) differ from it by about the tolerance.  The element-wise claim is therefore made by the oracle in float64 --
+    # which is the reference's float64 evaluation (1e-9) and is the same on every host -- and the oracle's fp32 result is held to the
+    # reference's fp32 one the way the GPU tests hold long reductions: as close to float64 (util.assert_fp64_anchored)
+    an = util.golden("fp64_anchor.npz")
+    d64 = {k: (v.double() if isinstance(v, torch.Tensor) and v.is_floating_point() else v) for k, v in _sg_inputs(g).items()}
+    sd64 = {k: (v.double() if v.is_floating_point() else v) for k, v in util.sg_sd(128).items()}
+    dn64 = superglue_ref.superglue_forward(d64, sd64, util.sg_config(128), return_dense=True)["dense"]
+    util.assert_close(dn64["scores_in"], an["sg_small/scores_in_f64"], "scores_in float64", atol=1e-9, rtol=1e-9)
+    util.assert_close(dn64["scores_in"], g["scores_in"], "scores_in", atol=1e-4, rtol=1e-5)
+    util.assert_fp64_anchored(dn["scores_in"], g["scores_in"], an["sg_small/scores_in_f64"], "oracle fp32 scores_in")
     util.assert_close(dn["Z"], g["Z"], "Z", atol=1e-4, rtol=1e-5)
     assert np.array_equal(out["matches0"].numpy(), g["matches0"])
     assert np.array_equal(out["matches1"].numpy(), g["matches1"])

@@ -1,13 +1,13 @@
 #!/bin/bash
 # Full measurement set for profiles/: bench JSON lines (c3 default, c2, c5), rocprofv3 kernel stats of the bench command,
 # and PMC passes (MFMA busy, FETCH_SIZE, WRITE_SIZE -- separate runs, kernel trace only) of the 64-pair step (the bench's own step).
-# usage: tools/gpu_profile_all.sh <tag>      -> gpurun_out/<tag>_*
+# usage: tools/gpu_profile_all.sh <tag>      -> $OUT_DIR/<tag>_* (default results/)
 tag=${1:-r06}
 R=$(pwd); export TMPDIR=/tmp
-out=$R/gpurun_out; mkdir -p $out
-python bench.py > $out/${tag}_bench_c3.json 2> $out/${tag}_bench_c3.log
-python bench.py --workload c2 --no-cpu-baseline --no-extras > $out/${tag}_bench_c2.json 2>/dev/null
-python bench.py --workload c5 --pairs-per-gpu 8 --steps 5 --no-cpu-baseline --no-extras > $out/${tag}_bench_c5.json 2>/dev/null
+out=${OUT_DIR:-$R/results}; mkdir -p $out
+python bench.py --full > $out/${tag}_bench_c3.json 2> $out/${tag}_bench_c3.log
+python bench.py --workload c2 --full --no-cpu-baseline --no-extras > $out/${tag}_bench_c2.json 2>/dev/null
+python bench.py --workload c5 --pairs-per-gpu 8 --steps 5 --full --no-cpu-baseline --no-extras > $out/${tag}_bench_c5.json 2>/dev/null
 prof() {  # name, rocprof args..., -- cmd
   name=$1; shift
   rm -rf $out/prof_tmp; mkdir -p $out/prof_tmp
