@@ -1058,10 +1058,10 @@ int sg_forward(imx_handle_t h, int B, const SgSide sd[2], int64_t* m0, int64_t* 
     a.n0 = sd[0].n; a.n1 = sd[1].n; a.N0 = N0; a.N1 = N1; a.cross = c.gnn_layer_is_cross[l];
     a.mfma_f32 = h->opt.mfma_f32; a.latency_forms = h->opt.latency_forms; a.qblocks = h->opt.attention_qblocks;
     const bool f16x2 = amax && attention_takes_x3(a) && (L.qkv_spread <= kAttnSpreadMax || h->opt.attention == 1);   // ("attention" = f16x2 forces it: the guard's A/B)
-    if (f16x2) {
-      if (!have_amax) RUN("qkv_amax", launch_qkv_amax(a, amax + 8 * B * l, s));
-      a.amax = amax + 8 * B * l;
-    }
+    if (f16x2) a.amax = amax + 8 * B * l;
+    // (the maxima also scale gnn_mlp1's [x | att] on the fp16 planes where lin_h2 holds -- max |v| bounds att -- so they are written for
+    // every layer then, also where the guard runs this layer's attention on bf16x3)
+    if ((f16x2 || lin_h2) && !have_amax) RUN("qkv_amax", launch_qkv_amax(a, amax + 8 * B * l, s));
     have_amax = false;
     RUN("attention", launch_attention(a, s));
     const bool last = l + 1 == h->layers.size();
@@ -1141,6 +1141,9 @@ int sg_forward(imx_handle_t h, int B, const SgSide sd[2], int64_t* m0, int64_t* 
     part = pt;
   }
   SinkhornArgs sk{S, u, v, B, N0p, N1p, sd[0].n, sd[1].n, N0, N1, h->bin_score, c.sinkhorn_iterations, part, h->opt.sinkhorn_group, h->opt.sinkhorn_prefetch};
+  // (slabs per workgroup: the group decides the merge order of the column partials, so under "latency_forms" = off the auto rule is
+  // evaluated at a fixed batch -- the potentials then do not depend on B, bit for bit)
+  if (h->opt.latency_forms == 0 && sk.group == 0) sk.group = sinkhorn_auto_group(N0p, N1p, kSinkhornOffBatch);
   if (part && h->opt.sinkhorn_merge > 0) {       // "sinkhorn_merge" = fused: the slab kernel merges its own column partials (auto = kernel: measured, sg_misc.hip)
     WS(mc, unsigned, "sg.sk_merge_cnt", ((size_t)B + 1) * sizeof(unsigned));
     sk.merge_cnt = mc;

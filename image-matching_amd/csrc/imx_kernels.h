@@ -26,7 +26,8 @@ struct Options {
   // A/B switches of the bit-identity tests and of tools/ (round 6: handle options; environment variables of these names are not read)
   int conv_swizzle = 1;    // "conv_swizzle": 1 = "on" (the tensor between two pair-form layers without a pool is tile-swizzled), 0 = "off" (blocked)
   int qkv_amax = 0;        // "qkv_amax": 0 = "epilogue" (a plain q|k|v projection's epilogue writes the (side, pair) maxima), 1 = "kernel" (the separate pass)
-  int sinkhorn_group = 0;  // "sinkhorn_group": 0 = "auto" (2 slabs per workgroup up to 1024 columns, 4 above, 1 below 64 slabs), 1 | 2 | 4
+  int sinkhorn_group = 0;  // "sinkhorn_group": 0 = "auto" (sinkhorn_auto_group: 4, 2 or 1 slabs per workgroup from the slab count and the batch size;
+                           //         under "latency_forms" = off from the slab count and a fixed batch of 64, so G does not depend on B), 1 | 2 | 4
   int sinkhorn_prefetch = -1;  // "sinkhorn_prefetch": -1 = "auto" (= off since round 6), 0 = "off", 1 = "on"
   int sinkhorn_merge = -1;     // "sinkhorn_merge": -1 = "auto" (= kernel), 0 = "kernel" (sinkhorn_vmerge, a second launch per iteration), 1 = "fused" (the last-arriving slab workgroups of a pair merge its column partials)
   int keypoints = -1;          // "keypoints": -1 = "auto" (candidate bit rows where the NMS is the staged form and the threshold >= 0), 0 = "dense" (the NMS score map, three passes), 1 = "bits"
@@ -316,6 +317,11 @@ struct SinkhornArgs {
                                          // slab-kernel workgroup of the LAST iteration -- s_memrealtime at entry / after each slab / at exit, HW_ID, XCC_ID
 };
 int sinkhorn_slab_rows(int N1p);
+// "sinkhorn_group" = auto: the most slabs per workgroup (4, 2, 1) whose groups of a B-pair batch still fill the resident workgroup slots
+// (1024 of the 8-wave slab form, N1p <= 1024; 512 of the 16-wave one).  The group decides the order the column partials are merged in,
+// so under "latency_forms" = off the caller evaluates it at a fixed B (kSinkhornOffBatch) to keep results independent of the batch size.
+int sinkhorn_auto_group(int N0p, int N1p, long B);
+constexpr long kSinkhornOffBatch = 64;
 hipError_t launch_sinkhorn(const SinkhornArgs& a, hipStream_t s);
 
 struct MatchArgs {

@@ -722,6 +722,14 @@ __global__ __launch_bounds__(256) void match_finalize(MatchArgs a) {
 // rows per LDS slab (R * N1p floats <= 64 KB); 0 = use the two-pass kernels
 int sinkhorn_slab_rows(int N1p) { return N1p <= 2048 ? 8 : N1p <= 4096 ? 4 : 0; }   // 16-row slabs measured slower (3.19 vs 2.36 ms at N = 1024)   // 8 rows even when 16 fit: 4 workgroups per CU (36 KB) hide the load latency better
 
+int sinkhorn_auto_group(int N0p, int N1p, long B) {
+  const int R = sinkhorn_slab_rows(N1p);
+  if (R <= 0) return 1;
+  const long nsl = N0p / R + 1;
+  const long slots = N1p <= 1024 ? 1024 : 512;
+  return (nsl + 3) / 4 * B >= slots ? 4 : (nsl + 1) / 2 * B >= slots ? 2 : 1;
+}
+
 
 hipError_t launch_sg_prologue(const SgPrologueArgs& a, hipStream_t s) {
   auto blocks = [](long n) { return (unsigned)((n + 255) / 256); };
@@ -798,9 +806,7 @@ hipError_t launch_sinkhorn(const SinkhornArgs& a, hipStream_t s) {
     // the groups of four still fill the 1024 workgroup slots of the 8-wave form)
     // the most slabs per workgroup (4, 2, 1) whose groups still fill the resident workgroup slots (1024 of the 8-wave form, 512 of the
     // 16-wave one): C3 x 1 pair 0.276 / 0.320 / 0.445 ms with 1 / 2 / 4, x 16 pairs 0.755 / 0.686 / 0.743, x 64 pairs - / 2.01 / 1.85
-    const int nsl = a.N0p / R + 1;
-    const long slots = a.N1p <= 1024 ? 1024 : 512;
-    int G = (long)((nsl + 3) / 4) * a.B >= slots ? 4 : (long)((nsl + 1) / 2) * a.B >= slots ? 2 : 1;
+    int G = sinkhorn_auto_group(a.N0p, a.N1p, a.B);
     if (a.group == 1 || a.group == 2 || a.group == 4) G = a.group;
     const int nslab_max = (a.N0p / R + 1 + G - 1) / G;           // groups per pair = the partial buffer's rows per pair (<= N0p / R + 1: a.part's size)
     // (Round 5: walking the batch in groups whose score matrices fit the 256-MB Infinity Cache -- all iterations of a group back to

@@ -224,7 +224,8 @@ IMX_API const char* imx_timing_form(imx_handle_t h, int index);
  *                           (the A/B reference the parity tests hold the default against);
  *   "latency_forms"  "auto" (default) one or two pairs take the latency forms of the linear layers (M <= 4096 rows) and of
  *                           the attention (grids of <= 256 workgroups) and one launch per GNN layer tail; "off" never (results
- *                           then do not depend on the batch size bit for bit); "on" whenever the shape allows; "unfused" = "on" with the GNN layer tail as three
+ *                           then do not depend on the batch size bit for bit: also the Sinkhorn group of "sinkhorn_group" = "auto"
+ *                           is then taken at a fixed batch of 64 pairs); "on" whenever the shape allows; "unfused" = "on" with the GNN layer tail as three
  *                           launches instead of one (same bytes: the A/B reference of the fused latency kernel);
  *   "conv"           "wino" (default) Winograd F(2x4,3x3) with its products on the fp16 matrix pipe: both transformed operands as two
  *                           fp16 planes scaled by a power of two (per tile in the fused first layer, per image -- from the producing
@@ -264,7 +265,8 @@ IMX_API const char* imx_timing_form(imx_handle_t h, int index);
  *   "conv_swizzle"      "on" (default) the tensor between two pair-form 3x3 layers without a pool is tile-swizzled; "off": blocked;
  *   "qkv_amax"          "epilogue" (default) a plain q|k|v projection writes the (side, pair) maxima in its epilogue; "kernel": a separate pass;
  *   "sinkhorn_group"    "auto" (default: the most slabs per workgroup -- 4, 2 or 1 -- whose groups still fill the chip's resident
- *                       workgroup slots: 1024 up to 1024 columns, 512 above) | "1" | "2" | "4";
+ *                       workgroup slots: 1024 up to 1024 columns, 512 above; under "latency_forms" = "off" the rule is evaluated at a
+ *                       fixed batch of 64 pairs, so the group depends on the padded keypoint counts only) | "1" | "2" | "4";
  *   "sinkhorn_prefetch" "auto" (default: off since round 6 -- two 16-wave workgroups per CU cover each other) | "off" | "on";
  *   "sinkhorn_merge"    "auto" (default: = "kernel") | "kernel" (sinkhorn_vmerge: a second launch per iteration) | "fused" (the last
  *                       slab workgroups of a pair merge its column partials: one launch per iteration, bit-identical, measured slower);

@@ -93,3 +93,16 @@ def stage_job(d, K, H, W, seed, own, strides=None):
     ident = np.arange(K)
     ref64 = run64(ref_data, ident, ident)
     return sp, res, {"own64": own64, "delta": {k: own64[k] - ref64[k] for k in own64}}
+
+
+def superglue_f64_job(sd, data, d):
+    """The oracle's SuperGlue in float64 on a caller's weight set `sd` (numpy arrays) and inputs `data` (numpy keypoints / scores /
+    descriptors per side, batch 1, plus image_shape0 / image_shape1): gnn17, scores_in, Z and the match indices."""
+    from oracle import superglue_ref
+    from tests import util
+    dat = {k: (torch.from_numpy(v).double() if isinstance(v, np.ndarray) and v.dtype.kind == "f" else v) for k, v in data.items()}
+    sd64 = {k: torch.from_numpy(np.asarray(v)).double() if np.asarray(v).dtype.kind == "f" else torch.from_numpy(np.asarray(v)) for k, v in sd.items()}
+    o = superglue_ref.superglue_forward(dat, sd64, util.sg_config(d), return_dense=True)
+    dn = o["dense"]
+    return {"gnn0": dn["gnn0"][0].numpy(), "gnn1": dn["gnn1"][0].numpy(), "scores_in": dn["scores_in"][0].numpy(), "Z": dn["Z"][0].numpy(),
+            "matches0": o["matches0"][0].numpy().astype(np.int64), "matches1": o["matches1"][0].numpy().astype(np.int64)}
