@@ -173,6 +173,8 @@ __global__ __launch_bounds__(256) void attention_kernel(AttnArgs p, float scale)
       // ---- online softmax over this tile's 32 keys (16 here, 16 in lane^32), log2 domain:
       //      p = 2^(s2 - m2) = e^(s - m); |abs err| of the one-multiply form <= 6e-8*max|x e^x| ~ 2e-8
       float mx = -INFINITY;
+      // (keys past nk: their scores become -inf, their weights 0 -- their V rows are still multiplied, so they must be FINITE: the
+      //  prologue zeroes the rows past a pair's count and every producer of q|k|v is row-wise, imx_api.cpp: sg_forward)
       if (kt * 32 + 32 <= nk) {           // full tile (block-uniform): no key masking
 #pragma unroll
         for (int r = 0; r < 16; ++r) mx = fmaxf(mx, S[r]);

@@ -303,6 +303,8 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(AttnArgs p, float 
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int key = kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+        // (FmtX3 multiplies the V rows of these keys by the zero weights: they are finite because the prologue zeroes the rows past a
+        //  pair's count, imx_api.cpp: sg_forward; FmtH2 zeroes the fragments above, its scales do not cover them)
         const float sv = key < nk ? S[r] : -INFINITY;
         S[r] = sv;
         mx = fmaxf(mx, sv);

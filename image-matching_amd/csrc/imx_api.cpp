@@ -124,6 +124,7 @@ struct imx_handle_s {
   std::string opt_text;      // backing store of imx_get_option's return value
   // debug / timing
   bool debug = false, timing = false;
+  int poison = -1;           // "debug_poison": the byte ws() fills a (re)allocated workspace with, -1 = off
   std::map<std::string, Tap> taps;
   std::vector<TimedEvent> events;
   std::vector<TimingRow> report;
@@ -147,10 +148,35 @@ int fail(imx_handle_t h, const char* fmt, ...) {
     if (e__ != hipSuccess) return fail(h, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
   } while (0)
 
+// "debug_poison" (imx_set_option; tests/test_gpu_history.py): which workspaces the hook may fill with a byte pattern.  The hook
+// writes VALUES into memory the library owns; it must never turn into a wild address or a wait that does not end.
+//   poisoned      every float workspace (sp.*, sg.*, tap.*, mp.desc*, knn.*, ransac.scratch, kp.cand_score, kp.sel_score): their
+//                 consumers read them as numbers only; and sg.amax / sp.amax (integer bit patterns of maxima): the forward zeroes
+//                 the whole table with hipMemsetAsync before the first kernel that reads or atomicMax-es it, on every call.
+//   never         sg.sk_merge_cnt (workgroup tickets a merging workgroup WAITS on), sg.sk_trace, sg.idx0 / sg.idx1 (column indices
+//                 that launch_matches turns into match indices), kp.row_count / row_off / cand_count / cand_idx / sel_count /
+//                 sel_idx / sort_slots (counts and pixel indices: loop bounds and gather addresses of the keypoint and describe
+//                 kernels), sp.nms_scratch / op.nms_scratch (candidate bit rows), mp.counts (per-pair counts: loop bounds of every
+//                 SuperGlue kernel).  Their consumers were not all read through for a bounds check, so they stay as they are.
+bool poisonable(const std::string& name) {
+  for (const char* no : {"sg.sk_merge_cnt", "sg.sk_trace", "sg.idx0", "sg.idx1", "kp.row_count", "kp.row_off", "kp.cand_count", "kp.cand_idx",
+                         "kp.sel_count", "kp.sel_idx", "kp.sort_slots", "sp.nms_scratch", "op.nms_scratch", "mp.counts"})
+    if (name == no) return false;
+  return true;
+}
+
+inline bool inside(const void* p, const DevBuf& b) {
+  return b.p && p >= b.p && static_cast<const char*>(p) < static_cast<const char*>(b.p) + b.bytes;
+}
+
 float* ws(imx_handle_t h, const std::string& name, size_t bytes) {
   DevBuf& b = h->bufs[name];
   if (b.bytes >= bytes && b.p) return static_cast<float*>(b.p);
   if (b.p) {
+    // nothing may keep a pointer into the buffer that goes away: the debug taps into it (the next forward registers them again) and
+    // the lazily materialised "nms" tap, whose inputs it may be
+    for (auto it = h->taps.begin(); it != h->taps.end();) it = inside(it->second.p, b) ? h->taps.erase(it) : std::next(it);
+    if (inside(h->nms_lazy.smap, b) || inside(h->nms_lazy.nms, b) || inside(h->nms_lazy.scratch, b)) h->nms_lazy.pending = false;
     (void)hipDeviceSynchronize();
     (void)hipFree(b.p);
     b.p = nullptr;
@@ -163,6 +189,10 @@ float* ws(imx_handle_t h, const std::string& name, size_t bytes) {
     return nullptr;
   }
   b.bytes = want;
+  if (h->poison >= 0 && poisonable(name) && (hipMemset(b.p, h->poison, want) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) {
+    h->err = "debug_poison: hipMemset failed for workspace '" + name + "'";
+    return nullptr;
+  }
   return static_cast<float*>(b.p);
 }
 #define WS(var, type, name, bytes)                         \
@@ -726,6 +756,7 @@ int gemm(imx_handle_t h, hipStream_t s, const char* name, const GemmW& W, const 
 int sp_detect(imx_handle_t h, const float* img0, const float* img1, int split, int B, int H, int W, int32_t* counts_out,
               hipStream_t s, bool dense_only = false, int32_t* counts_lo = nullptr, int32_t* counts_hi = nullptr) {
   if (!h->finalized[IMX_NET_SUPERPOINT]) return fail(h, "SuperPoint weights not finalized");
+  h->nms_lazy.pending = false;       // (the maps it points at are about to be overwritten; set again at the end of a detect that ran the bit form)
   if (B <= 0 || H < 8 || W < 8) return fail(h, "bad image batch shape B=%d H=%d W=%d", B, H, W);
   const imx_config_t& c = h->cfg;
   const int H2 = H / 2, W2 = W / 2, H4 = H2 / 2, W4 = W2 / 2, Hc = H4 / 2, Wc = W4 / 2, H8 = Hc * 8, W8 = Wc * 8;
@@ -961,6 +992,11 @@ int sg_forward(imx_handle_t h, int B, const SgSide sd[2], int64_t* m0, int64_t* 
   WS(idx1, int, "sg.idx1", (size_t)B * N1p * 4);
 
   // descriptors -> rows; first keypoint-encoder layer (superglue_test.py:245-250): both sides, one launch
+  // (with the per-pair counts: rows n[b] .. Np-1 of x and of the encoder's first layer are ZEROS whatever the caller's tensors hold
+  // there.  Every later kernel is row-wise or masks by the counts, so a padding row stays finite for the whole forward -- which the
+  // bf16x3 and fp32 attention kernels rely on: they mask the SCORES of keys past the count and still multiply those keys' V rows by
+  // the zero weights (0 x NaN would reach every query row); only the fp16-plane form zeroes the K / V fragments itself.
+  // tests/test_gpu_padding.py fills the caller's padding with NaN / Inf / 3e38 on every form.)
   {
     SgPrologueArgs pa{};
     pa.d = d;
@@ -970,7 +1006,7 @@ int sg_forward(imx_handle_t h, int B, const SgSide sd[2], int64_t* m0, int64_t* 
       pa.desc[sidx] = q.desc; pa.sb[sidx] = (long)q.sb; pa.sc[sidx] = (long)q.sc; pa.sn[sidx] = (long)q.sn;
       pa.xrow[sidx] = x + (sidx ? off1 : 0) * d;
       Kenc0Args& k = pa.k[sidx];
-      k.kpts = q.kpts; k.scores = q.scores; k.B = B; k.N = q.N; k.Np = Np;
+      k.kpts = q.kpts; k.scores = q.scores; k.B = B; k.N = q.N; k.Np = Np; k.n = q.n;
       k.cx = (float)q.W / 2.0f; k.cy = (float)q.H / 2.0f;
       k.scaling = (float)std::max(q.W, q.H) * 0.7f;
       k.w = h->kenc0_w; k.bias = h->kenc0_b; k.C1 = h->kenc_c1;
@@ -1174,7 +1210,8 @@ int sg_forward(imx_handle_t h, int B, const SgSide sd[2], int64_t* m0, int64_t* 
 
 // "mfma" = x3 | f32, "latency_forms" = auto | off | on | unfused, "conv" = wino | wino_h | wino32 | direct, "gnn_tail" = auto | fused | bf16x3 | unfused, "attention" = auto | f16x2 | bf16x3,
 // "linear" = auto | f16x2 | bf16x3;
-// the A/B switches "conv_swizzle" = on | off, "qkv_amax" = epilogue | kernel, "sinkhorn_group" = auto | 1 | 2 | 4, "sinkhorn_prefetch" = auto | off | on.  Returns 0, or -1 for an unknown key / value.
+// the A/B switches "conv_swizzle" = on | off, "qkv_amax" = epilogue | kernel, "sinkhorn_group" = auto | 1 | 2 | 4, "sinkhorn_prefetch" = auto | off | on;
+// the test hook "debug_poison" = off | nan | huge | zero (poisonable() above).  Returns 0, or -1 for an unknown key / value.
 int apply_option(imx_handle_t h, const std::string& key, const std::string& v) {
   Options& o = h->opt;
   if (key == "mfma") {
@@ -1212,6 +1249,18 @@ int apply_option(imx_handle_t h, const std::string& key, const std::string& v) {
     if (v == "auto") o.keypoints = -1; else if (v == "dense") o.keypoints = 0; else if (v == "bits") o.keypoints = 1; else return -1;
   } else if (key == "sinkhorn_prefetch") {
     if (v == "auto") o.sinkhorn_prefetch = -1; else if (v == "off" || v == "0") o.sinkhorn_prefetch = 0; else if (v == "on" || v == "1") o.sinkhorn_prefetch = 1; else return -1;
+  } else if (key == "debug_poison") {
+    // the byte pattern as floats: 0xFF.. a NaN, 0x7F7F7F7F = 3.4e38, 0
+    int byte;
+    if (v == "off") byte = -1; else if (v == "nan") byte = 0xFF; else if (v == "huge") byte = 0x7F; else if (v == "zero") byte = 0x00; else return -1;
+    if (byte >= 0) {
+      if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return -1;
+      for (auto& kv : h->bufs)
+        if (kv.second.p && poisonable(kv.first) && hipMemset(kv.second.p, byte, kv.second.bytes) != hipSuccess) return -1;
+      if (hipDeviceSynchronize() != hipSuccess) return -1;
+      h->nms_lazy.pending = false;   // (its inputs are gone: the "nms" tap now reads what every other tap reads, the pattern)
+    }
+    h->poison = byte;
   } else {
     return -1;
   }
@@ -1563,8 +1612,8 @@ int imx_knn_ratio_match(imx_handle_t h, int B, const float* desc0_dev, int64_t s
     WS(nr0, float, "knn.norm0", (size_t)B * N0p * f);
     WS(nr1, float, "knn.norm1", (size_t)B * N1p * f);
     WS(dots, float, "knn.dots", (size_t)B * N0p * N1p * f);
-    RUN("gather_desc", launch_gather_desc(desc0_dev, s0b, s0c, s0n, B, N0, N0p, d, r0, s));
-    RUN("gather_desc", launch_gather_desc(desc1_dev, s1b, s1c, s1n, B, N1, N1p, d, r1, s));
+    RUN("gather_desc", launch_gather_desc(desc0_dev, s0b, s0c, s0n, B, N0, N0p, d, n0_dev, r0, s));
+    RUN("gather_desc", launch_gather_desc(desc1_dev, s1b, s1c, s1n, B, N1, N1p, d, n1_dev, r1, s));
     RUN("rownorm2", launch_rownorm2(r0, d, (long)B * N0p, nr0, s));
     RUN("rownorm2", launch_rownorm2(r1, d, (long)B * N1p, nr1, s));
     ScoreArgs sc{r0, r1, dots, B, N0p, N1p, d, 1.0f};
@@ -1709,7 +1758,7 @@ int imx_set_option(imx_handle_t h, const char* key, const char* value) {
   return guarded(h, "imx_set_option", [&]() -> int {
     if (!h) return -1;
     if (!key || !value) return fail(h, "imx_set_option: null argument");
-    if (apply_option(h, key, value)) return fail(h, "imx_set_option: unknown option or value '%s' = '%s' (mfma = x3|f32, latency_forms = auto|off|on|unfused, conv = wino|wino_h|wino32|direct, gnn_tail = auto|fused|bf16x3|unfused, attention = auto|f16x2|bf16x3, linear = auto|f16x2|bf16x3, attention_qblocks = auto|1|2, conv_swizzle = on|off, qkv_amax = epilogue|kernel, sinkhorn_group = auto|1|2|4, sinkhorn_prefetch = auto|off|on, sinkhorn_merge = auto|kernel|fused, keypoints = auto|dense|bits)", key, value);
+    if (apply_option(h, key, value)) return fail(h, "imx_set_option: unknown option or value '%s' = '%s' (mfma = x3|f32, latency_forms = auto|off|on|unfused, conv = wino|wino_h|wino32|direct, gnn_tail = auto|fused|bf16x3|unfused, attention = auto|f16x2|bf16x3, linear = auto|f16x2|bf16x3, attention_qblocks = auto|1|2, conv_swizzle = on|off, qkv_amax = epilogue|kernel, sinkhorn_group = auto|1|2|4, sinkhorn_prefetch = auto|off|on, sinkhorn_merge = auto|kernel|fused, keypoints = auto|dense|bits, debug_poison = off|nan|huge|zero)", key, value);
     return 0;
   });
 }
@@ -1732,6 +1781,7 @@ const char* imx_get_option(imx_handle_t h, const char* key) {
     else if (k == "sinkhorn_prefetch") h->opt_text = o.sinkhorn_prefetch < 0 ? "auto" : o.sinkhorn_prefetch ? "on" : "off";
     else if (k == "sinkhorn_merge") h->opt_text = o.sinkhorn_merge < 0 ? "auto" : o.sinkhorn_merge ? "fused" : "kernel";
     else if (k == "keypoints") h->opt_text = o.keypoints < 0 ? "auto" : o.keypoints ? "bits" : "dense";
+    else if (k == "debug_poison") h->opt_text = h->poison < 0 ? "off" : h->poison == 0xFF ? "nan" : h->poison == 0x7F ? "huge" : "zero";
     else if (k == "arith_guard") {      // read-only: what the weights-derived guards decided (after imx_finalize_weights)
       char buf[96];
       float sp = h->c1a_spread;

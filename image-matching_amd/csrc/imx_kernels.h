@@ -227,23 +227,24 @@ hipError_t launch_describe(const DescribeArgs& a, hipStream_t s);
 struct Kenc0Args {
   const float* kpts; const float* scores;  // (B,N,2), (B,N)
   int B, N, Np;                            // Np = padded rows per image in the internal layout
+  const int* n;                            // valid rows per pair (device), may be null => N; rows n[b] .. N-1 of kpts / scores are never read
   float cx, cy, scaling;                   // center and scaling (superglue_test.py:63-70)
   const float* w; const float* bias;       // [3][C1], [C1]
   int C1;
-  float* out;                              // rows (b*Np + i), ld = C1; rows >= N zeroed
+  float* out;                              // rows (b*Np + i), ld = C1; rows >= n[b] zeroed
 };
 // SuperGlue's prologue for BOTH sides in one launch: the descriptor gather and the first keypoint-encoder layer (four launches of
 // ~4.5 us each on the single-pair path).  Same per-element arithmetic as launch_gather_desc / launch_kenc0.
 struct SgPrologueArgs {
   const float* desc[2]; long sb[2], sc[2], sn[2];   // descriptors (arbitrary strides) per side
-  float* xrow[2];                                    // rows (b*Np + i), ld = d
+  float* xrow[2];                                    // rows (b*Np + i), ld = d; rows >= k[side].n[b] zeroed
   Kenc0Args k[2];                                    // B, N, Np per side in here
   int d;
 };
 hipError_t launch_sg_prologue(const SgPrologueArgs& a, hipStream_t s);
-// copy descriptors (arbitrary strides) into rows (b*Np+i), ld=d; rows >= N zero.
+// copy descriptors (arbitrary strides) into rows (b*Np+i), ld=d; rows >= n[b] (n null: >= N) are zeros, whatever the source holds there.
 hipError_t launch_gather_desc(const float* src, int64_t sb, int64_t sc, int64_t sn, int B, int N, int Np, int d,
-                              float* out, hipStream_t s);
+                              const int* n, float* out, hipStream_t s);
 
 // flash-style multi-head attention, fp32 MFMA.  qkv rows: [side0: B*N0p rows][side1: B*N1p rows],
 // ld = 3*d, columns [q | k | v], each head-major (head*32 + dim).  out same rows, ld = d.

@@ -85,15 +85,18 @@ __device__ __forceinline__ float uniform_f(float v) { return __builtin_bit_cast(
 __device__ __forceinline__ float lse_unbias(float sum, float mx, float ml) { return fmaf(sum, -0.69314718f * fmaf(mx, LOG2E, ml), sum); }
 
 // ------------------------------------------------------------------ kenc layer 0
+// (rows past a pair's valid count are the caller's padding: it may hold anything, NaN included, and is never read -- the rows are zeros)
+__device__ __forceinline__ int valid_rows(const int* n, int b, int N) { return n ? min(max(n[b], 0), N) : N; }
+
 __global__ __launch_bounds__(256) void gather_desc_kernel(const float* __restrict__ src, long sb, long sc, long sn,
-                                                          int B, int N, int Np, int d, float* __restrict__ out) {
+                                                          int B, int N, int Np, int d, const int* __restrict__ n, float* __restrict__ out) {
   const long e = (long)blockIdx.x * 256 + threadIdx.x;
   const long total = (long)B * Np * d;
   if (e >= total) return;
   const int c = (int)(e % d);
   const long row = e / d;
   const int i = (int)(row % Np), b = (int)(row / Np);
-  out[e] = i < N ? src[b * sb + c * sc + i * sn] : 0.f;
+  out[e] = i < valid_rows(n, b, N) ? src[b * sb + c * sc + i * sn] : 0.f;
 }
 
 // both sides' gather + kenc layer 0 in one grid: blocks [0, g0) gather side 0, [g0, k0) kenc0 side 0, [k0, g1) gather side 1,
@@ -105,7 +108,7 @@ __device__ __forceinline__ void kenc0_element(const Kenc0Args& a, long e) {
   const long row = e / a.C1;
   const int i = (int)(row % a.Np), b = (int)(row / a.Np);
   float v = 0.f;
-  if (i < a.N) {
+  if (i < valid_rows(a.n, b, a.N)) {
     const float* kp = a.kpts + ((size_t)b * a.N + i) * 2;
     const float xn = (kp[0] - a.cx) / a.scaling;          // normalize_keypoints (:63-70)
     const float yn = (kp[1] - a.cy) / a.scaling;
@@ -130,7 +133,7 @@ __global__ __launch_bounds__(256) void sg_prologue_kernel(SgPrologueArgs a, unsi
     const int c = (int)(e % a.d);
     const long row = e / a.d;
     const int i = (int)(row % k.Np), b = (int)(row / k.Np);
-    a.xrow[side][e] = i < k.N ? a.desc[side][b * a.sb[side] + c * a.sc[side] + i * a.sn[side]] : 0.f;
+    a.xrow[side][e] = i < valid_rows(k.n, b, k.N) ? a.desc[side][b * a.sb[side] + c * a.sc[side] + i * a.sn[side]] : 0.f;
   } else {
     kenc0_element(k, (long)(blk - gend) * 256 + threadIdx.x);
   }
@@ -740,10 +743,10 @@ hipError_t launch_sg_prologue(const SgPrologueArgs& a, hipStream_t s) {
 }
 
 hipError_t launch_gather_desc(const float* src, int64_t sb, int64_t sc, int64_t sn, int B, int N, int Np, int d,
-                              float* out, hipStream_t s) {
+                              const int* n, float* out, hipStream_t s) {
   long total = (long)B * Np * d;
   hipLaunchKernelGGL(gather_desc_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, (long)sb, (long)sc,
-                     (long)sn, B, N, Np, d, out);
+                     (long)sn, B, N, Np, d, n, out);
   return hipGetLastError();
 }
 

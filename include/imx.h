@@ -111,6 +111,7 @@ IMX_API int imx_superpoint_dense(imx_handle_t h, const float* img_dev, int B, in
  *   desc{0,1}_dev: element (b, c, i) at  b*desc_stride_b + c*desc_stride_c + i*desc_stride_n
  *                  (reference layout (B,d,N): stride_c = N, stride_n = 1);
  *   n{0,1}_dev: B int32 valid counts per pair, or NULL = all N{0,1} valid;
+ *               rows past the count (of kpts, scores and desc) may hold anything, including NaN: they are never read;
  *   H,W per side: only the image *shape* is used (normalize_keypoints, :63-70).
  * Outputs (B,N0)/(B,N1): matches int64 (-1 = unmatched), matching_scores fp32; entries at
  * i >= count are -1 / 0.  A pair with a zero count yields all -1 / 0 (:235-242). */
@@ -273,6 +274,12 @@ IMX_API const char* imx_timing_form(imx_handle_t h, int index);
  *   "keypoints"         "auto" (default: "bits" where nms_radius is 1..4 and keypoint_threshold >= 0, else "dense") | "dense" (the
  *                       keypoint kernels read the NMS'd score map, three passes) | "bits" (they read the candidate bit rows the last
  *                       NMS stage writes; the "nms" debug tap is then computed when it is fetched).
+ * Test hook (never in production; not read from the environment):
+ *   "debug_poison"      "off" (default) | "nan" | "huge" | "zero": fills every float workspace the handle holds (and the maxima
+ *                       tables the forward zeroes itself) with the byte 0xFF (a NaN) / 0x7F (3.4e38) / 0x00, synchronously, and
+ *                       every workspace allocated or grown afterwards with the same byte.  Weights, integer index / count /
+ *                       ticket buffers and the caller's tensors are never touched.  A result that changes under it read memory
+ *                       that the call did not write (tests/test_gpu_history.py).  "off" costs one branch per allocation.
  * Read-only (imx_get_option only): "arith_guard" -- what the weights-derived guards decided at imx_finalize_weights: the largest spread
  * of a layer's transformed convolution weights and the pipe the 3x3 chain runs on, the GNN layers whose tail runs bf16x3, the largest
  * bound looseness, the layers whose attention runs bf16x3 with the largest q|k|v channel spread, the largest spread of the plain
