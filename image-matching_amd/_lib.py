@@ -14,7 +14,8 @@ SP_VARIANT_BN, SP_VARIANT_OFFICIAL = 0, 1
 EXPORTS = (
     "imx_create", "imx_destroy", "imx_last_error", "imx_load_weight", "imx_finalize_weights",
     "imx_superpoint_detect", "imx_superpoint_describe", "imx_superpoint_dense", "imx_superglue_forward",
-    "imx_match_pairs", "imx_pack_records", "imx_gather_records", "imx_estimate_affine_partial", "imx_knn_ratio_match", "imx_ingest_resize_u8", "imx_warp_affine_u8", "imx_op_nms", "imx_set_debug", "imx_debug_fetch", "imx_set_timing",
+    "imx_match_pairs", "imx_pack_records", "imx_gather_records", "imx_estimate_affine_partial", "imx_knn_ratio_match", "imx_ingest_resize_u8", "imx_warp_affine_u8", "imx_op_nms",
+    "imx_warp_homography", "imx_combine_heatmap", "imx_superpoint_heatmap", "imx_homography_adapt", "imx_heatmap_points", "imx_set_debug", "imx_debug_fetch", "imx_set_timing",
     "imx_timing_report", "imx_timing_reset", "imx_timing_form", "imx_set_option", "imx_get_option", "imx_version",
 )
 
@@ -77,6 +78,11 @@ def load_library():
     lib.imx_ingest_resize_u8.argtypes = [vp, vp, i32, i32, i32, i64, f32p, i32, i32, vp]
     lib.imx_warp_affine_u8.argtypes = [vp, vp, i32, i32, ctypes.POINTER(ctypes.c_double), vp, i32, i32, vp]
     lib.imx_op_nms.argtypes = [vp, f32p, f32p, i32, i32, i32, i32, vp]
+    lib.imx_warp_homography.argtypes = [vp, f32p, i32, i32, i32, i32, f32p, i32, f32p, vp]
+    lib.imx_combine_heatmap.argtypes = [vp, f32p, f32p, f32p, i32, i32, i32, f32p, f32p, vp]
+    lib.imx_superpoint_heatmap.argtypes = [vp, f32p, i32, i32, i32, f32p, vp]
+    lib.imx_homography_adapt.argtypes = [vp, f32p, i32, i32, i32, f32p, f32p, f32p, f32p, vp]
+    lib.imx_heatmap_points.argtypes = [vp, f32p, i32, i32, ctypes.c_float, i32, i32, i32, f32p, i32, vp, vp]
     lib.imx_set_debug.argtypes = [vp, i32]
     lib.imx_debug_fetch.argtypes = [vp, ctypes.c_char_p, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i32)]
     lib.imx_set_timing.argtypes = [vp, i32]

@@ -754,7 +754,7 @@ int gemm(imx_handle_t h, hipStream_t s, const char* name, const GemmW& W, const 
 
 // ----------------------------------------------------------------------------- SuperPoint
 int sp_detect(imx_handle_t h, const float* img0, const float* img1, int split, int B, int H, int W, int32_t* counts_out,
-              hipStream_t s, bool dense_only = false, int32_t* counts_lo = nullptr, int32_t* counts_hi = nullptr) {
+              hipStream_t s, bool dense_only = false, int32_t* counts_lo = nullptr, int32_t* counts_hi = nullptr, bool det_only = false) {
   if (!h->finalized[IMX_NET_SUPERPOINT]) return fail(h, "SuperPoint weights not finalized");
   h->nms_lazy.pending = false;       // (the maps it points at are about to be overwritten; set again at the end of a detect that ran the bit form)
   if (B <= 0 || H < 8 || W < 8) return fail(h, "bad image batch shape B=%d H=%d W=%d", B, H, W);
@@ -773,9 +773,13 @@ int sp_detect(imx_handle_t h, const float* img0, const float* img1, int split, i
   WS(x4, float, "sp.x4", (size_t)B * Hc * Wc * 128 * f);
   WS(hd, float, "sp.heads", (size_t)B * Hc * Wc * 512 * f);
   WS(semi, float, "sp.semi", (size_t)B * Hc * Wc * 65 * f);
-  WS(dense, float, "sp.dense", (size_t)B * Hc * Wc * d * f);
-  WS(smap, float, "sp.score_map", (size_t)B * H8 * W8 * f);
-  WS(nms, float, "sp.nms", (size_t)B * H8 * W8 * f);
+  // (the descriptor map is not needed by a detector-only forward, the score / NMS maps by neither dense form: at 480 x 640, N = 100
+  // that is ~490 MB a homographic-adaptation call never asks for)
+  float* dense = nullptr;
+  if (!det_only) {
+    WS(dense_, float, "sp.dense", (size_t)B * Hc * Wc * d * f);
+    dense = dense_;
+  }
 
   // Activations between the Winograd layers are channel-blocked (B, C/8, H, W, 8) -- dense patch loads for the next layer
   // (conv3x3_wino24.hip); the last 3x3 layer writes NHWC rows for the 1x1-conv GEMMs.  IMX_CONV=direct (or a layer the Winograd
@@ -881,12 +885,27 @@ int sp_detect(imx_handle_t h, const float* img0, const float* img1, int split, i
   if (conv("conv3b_pool", h->conv[4], a3a, a3, H4, W4, true, false)) return -1;
   if (conv("conv4a", h->conv[5], a3, a4a, Hc, Wc, false, false)) return -1;
   if (conv("conv4b", h->conv[6], a4a, x4, Hc, Wc, false, false)) return -1;
-  if (conv("convPaDa", h->conv[7], x4, hd, Hc, Wc, false, false, true)) return -1;
+  // det_only (imx_homography_adapt: only `semi` is consumed): the descriptor head is not run.  convPa | convDa share one launch whose
+  // Winograd weights are laid out by 64-channel output block, convPa's four blocks first, so a Cout = 256 view of the same buffers IS
+  // convPa alone; the direct form's [9][Cin][Cout] weights have no such prefix, so there (and where the Winograd kernels reject the
+  // narrower shape) the shared launch stays and only convDb is skipped.
+  ConvW heads = h->conv[7];
+  int hd_ld = 512;
+  if (det_only && blocked) {
+    ConvArgs t{};
+    t.B = std::min(B, kSlice); t.H = Hc; t.W = Wc; t.Cin = heads.cin; t.Cout = 256; t.wu24 = heads.wu24;
+    bool ok = conv3x3_wino24_supported(t);
+    if (ok && amax) { t.wuh = heads.wuh; t.u_scale_inv = heads.su_inv; t.amax_in = amax; ok = conv3x3_wino24h_supported(t); }
+    if (ok) { heads.cout = 256; hd_ld = 256; }
+  }
+  if (conv(hd_ld == 256 ? "convPa" : "convPaDa", heads, x4, hd, Hc, Wc, false, false, true)) return -1;
   const int rows = B * Hc * Wc;
-  if (gemm(h, s, "convPb", h->pb, hd, 512, 256, nullptr, 0, 0, nullptr, 0, semi, 65, rows, false)) return -1;
-  if (gemm(h, s, "convDb", h->db, hd + 256, 512, 256, nullptr, 0, 0, nullptr, 0, dense, d, rows, false)) return -1;
+  if (gemm(h, s, "convPb", h->pb, hd, hd_ld, 256, nullptr, 0, 0, nullptr, 0, semi, 65, rows, false)) return -1;
+  if (!det_only && gemm(h, s, "convDb", h->db, hd + 256, 512, 256, nullptr, 0, 0, nullptr, 0, dense, d, rows, false)) return -1;
   h->det_Hc = Hc; h->det_Wc = Wc;
   if (dense_only) { h->det_B = 0; h->nms_lazy.pending = false; return 0; }     // network only (imx_superpoint_dense)
+  WS(smap, float, "sp.score_map", (size_t)B * H8 * W8 * f);
+  WS(nms, float, "sp.nms", (size_t)B * H8 * W8 * f);
   RUN("softmax_shuffle", launch_softmax_shuffle(semi, 65, smap, B, Hc, Wc, s));
   WS(nms_scratch, unsigned, "sp.nms_scratch", nms_scratch_bytes(B, H8, W8, c.nms_radius));
   // Round 6: NMS + threshold + remove_borders leave the detector as candidate BIT rows (20 words per 640-pixel row) and the keypoint kernels
@@ -1237,6 +1256,8 @@ int apply_option(imx_handle_t h, const std::string& key, const std::string& v) {
     if (v == "auto") o.attention_qblocks = -1; else if (v == "1") o.attention_qblocks = 1; else if (v == "2") o.attention_qblocks = 2; else return -1;
   } else if (key == "linear") {
     if (v == "auto") o.linear = -1; else if (v == "f16x2" || v == "1") o.linear = 1; else if (v == "bf16x3" || v == "x3" || v == "0") o.linear = 0; else return -1;
+  } else if (key == "ha_masks") {
+    if (v == "stored") o.ha_masks = 0; else if (v == "recompute") o.ha_masks = 1; else return -1;
   } else if (key == "conv_swizzle") {
     if (v == "on" || v == "1") o.conv_swizzle = 1; else if (v == "off" || v == "0") o.conv_swizzle = 0; else return -1;
   } else if (key == "qkv_amax") {
@@ -1657,6 +1678,100 @@ int imx_warp_affine_u8(imx_handle_t h, const uint8_t* src_dev, int Hs, int Ws, c
   });
 }
 
+int imx_warp_homography(imx_handle_t h, const float* src_dev, int src_shared, int N, int H, int W, const float* mats_dev, int nearest,
+                        float* dst_dev, void* stream) {
+  return guarded(h, "imx_warp_homography", [&]() -> int {
+    if (!h) return -1;
+    HIP_OK(h, hipSetDevice(h->device));
+    if (N < 1 || N > 65535 || H < 2 || W < 2) return fail(h, "imx_warp_homography: bad shape N=%d H=%d W=%d (N in [1,65535], H, W >= 2)", N, H, W);
+    if (!mats_dev || !dst_dev) return fail(h, "imx_warp_homography: null argument");
+    hipStream_t s = as_stream(stream);
+    RUN("ha_warp", launch_ha_warp(src_dev, src_shared ? 0 : (long)H * W, mats_dev, N, H, W, nearest != 0, dst_dev, nullptr, s));
+    return 0;
+  });
+}
+
+int imx_combine_heatmap(imx_handle_t h, const float* heat_dev, const float* mask_dev, const float* unwarp_dev, int N, int H, int W,
+                        float* out_dev, float* count_dev, void* stream) {
+  return guarded(h, "imx_combine_heatmap", [&]() -> int {
+    if (!h) return -1;
+    HIP_OK(h, hipSetDevice(h->device));
+    if (N < 1 || H < 2 || W < 2) return fail(h, "imx_combine_heatmap: bad shape N=%d H=%d W=%d (N >= 1, H, W >= 2)", N, H, W);
+    if (!heat_dev || !mask_dev || !unwarp_dev || !out_dev) return fail(h, "imx_combine_heatmap: null argument");
+    hipStream_t s = as_stream(stream);
+    RUN("ha_combine", launch_ha_combine(heat_dev, mask_dev, nullptr, unwarp_dev, N, H, W, out_dev, count_dev, s));
+    return 0;
+  });
+}
+
+int imx_superpoint_heatmap(imx_handle_t h, const float* img_dev, int B, int H, int W, float* heat_dev, void* stream) {
+  return guarded(h, "imx_superpoint_heatmap", [&]() -> int {
+    if (!h) return -1;
+    HIP_OK(h, hipSetDevice(h->device));
+    if (H < 8 || W < 8 || H % 8 || W % 8) return fail(h, "imx_superpoint_heatmap: H and W must be multiples of 8 (got %d x %d)", H, W);
+    if (!img_dev || !heat_dev) return fail(h, "imx_superpoint_heatmap: null argument");
+    hipStream_t s = as_stream(stream);
+    if (sp_detect(h, img_dev, nullptr, B, B, H, W, nullptr, s, true, nullptr, nullptr, true)) return -1;
+    RUN("ha_heat", launch_softmax_shuffle(static_cast<const float*>(h->bufs["sp.semi"].p), 65, heat_dev, B, H / 8, W / 8, s));
+    return 0;
+  });
+}
+
+int imx_homography_adapt(imx_handle_t h, const float* img_dev, int H, int W, int N, const float* warp_dev, const float* unwarp_dev,
+                         float* heatmap_dev, float* count_dev, void* stream) {
+  return guarded(h, "imx_homography_adapt", [&]() -> int {
+    if (!h) return -1;
+    HIP_OK(h, hipSetDevice(h->device));
+    if (N < 1 || N > 65535) return fail(h, "imx_homography_adapt: N must be in [1,65535] (got %d)", N);
+    if (H < 8 || W < 8 || H % 8 || W % 8) return fail(h, "imx_homography_adapt: H and W must be multiples of 8 (got %d x %d)", H, W);
+    if (!img_dev || !warp_dev || !unwarp_dev || !heatmap_dev) return fail(h, "imx_homography_adapt: null argument");
+    if (!h->finalized[IMX_NET_SUPERPOINT]) return fail(h, "SuperPoint weights not finalized");
+    hipStream_t s = as_stream(stream);
+    const size_t stack = (size_t)N * H * W * sizeof(float);
+    WS(warped, float, "ha.warped", stack);
+    // "ha_masks" = recompute: no mask stack (the combine evaluates the predicate itself) unless the debug tap wants it
+    const bool stored = h->opt.ha_masks == 0 || h->debug;
+    float* mask = nullptr;
+    if (stored) {
+      WS(mask_, float, "ha.mask", stack);
+      mask = mask_;
+    }
+    WS(heat, float, "ha.heat", stack);
+    // the N warps of the ONE image (the reference's repeat is never materialised) and their valid masks in one launch
+    RUN("ha_warp", launch_ha_warp(img_dev, 0, warp_dev, N, H, W, 0, warped, mask, s));
+    if (sp_detect(h, warped, nullptr, N, N, H, W, nullptr, s, true, nullptr, nullptr, true)) return -1;
+    RUN("ha_heat", launch_softmax_shuffle(static_cast<const float*>(h->bufs["sp.semi"].p), 65, heat, N, H / 8, W / 8, s));
+    RUN("ha_combine", launch_ha_combine(heat, h->opt.ha_masks == 0 ? mask : nullptr, warp_dev, unwarp_dev, N, H, W, heatmap_dev, count_dev, s));
+    tap(h, "ha_warped", warped, {N, H, W});
+    // (the only tap that is ever withdrawn: without a stored stack an "ha_mask" left by an earlier call would point at masks of OTHER
+    // matrices, and imx_debug_fetch would hand them out as this call's)
+    if (mask) tap(h, "ha_mask", mask, {N, H, W}); else h->taps.erase("ha_mask");
+    tap(h, "ha_heat", heat, {N, H, W});
+    return 0;
+  });
+}
+
+int imx_heatmap_points(imx_handle_t h, const float* heatmap_dev, int H, int W, float conf_thresh, int nms_dist, int top_k, int subpixel,
+                       float* pts_dev, int cap, int32_t* count_dev, void* stream) {
+  return guarded(h, "imx_heatmap_points", [&]() -> int {
+    if (!h) return -1;
+    HIP_OK(h, hipSetDevice(h->device));
+    if (H < 1 || W < 1 || (int64_t)H * W > (1 << 30)) return fail(h, "imx_heatmap_points: bad map shape %d x %d", H, W);
+    if (nms_dist < 0) return fail(h, "imx_heatmap_points: nms_dist must be >= 0 (got %d)", nms_dist);
+    if (cap < 0 || (cap > 0 && !pts_dev) || !heatmap_dev) return fail(h, "imx_heatmap_points: null argument or negative cap");
+    hipStream_t s = as_stream(stream);
+    WS(scratch, char, "hp.scratch", heatmap_points_scratch_bytes(H, W));
+    HeatmapPointsArgs a{};
+    a.heatmap = heatmap_dev; a.H = H; a.W = W; a.conf_thresh = conf_thresh; a.nms_dist = nms_dist; a.border = 4; a.top_k = top_k;
+    a.subpixel = subpixel != 0; a.pts = pts_dev; a.cap = cap; a.count = count_dev; a.scratch = scratch;
+    RUN("heatmap_points", launch_heatmap_points(a, s));
+    // the scratch's counter words: [0 .. kHeatmapPointsRounds) pixels still undecided after each bounded round, then how many the
+    // unbounded pass took over, then the survivors inside the border (32-bit integers; the fetch copies their bit patterns)
+    tap(h, "hp_counters", scratch, {16});
+    return 0;
+  });
+}
+
 int imx_set_debug(imx_handle_t h, int enable) {
   return guarded(h, "imx_set_debug", [&]() -> int {
     if (!h) return -1;
@@ -1758,7 +1873,7 @@ int imx_set_option(imx_handle_t h, const char* key, const char* value) {
   return guarded(h, "imx_set_option", [&]() -> int {
     if (!h) return -1;
     if (!key || !value) return fail(h, "imx_set_option: null argument");
-    if (apply_option(h, key, value)) return fail(h, "imx_set_option: unknown option or value '%s' = '%s' (mfma = x3|f32, latency_forms = auto|off|on|unfused, conv = wino|wino_h|wino32|direct, gnn_tail = auto|fused|bf16x3|unfused, attention = auto|f16x2|bf16x3, linear = auto|f16x2|bf16x3, attention_qblocks = auto|1|2, conv_swizzle = on|off, qkv_amax = epilogue|kernel, sinkhorn_group = auto|1|2|4, sinkhorn_prefetch = auto|off|on, sinkhorn_merge = auto|kernel|fused, keypoints = auto|dense|bits, debug_poison = off|nan|huge|zero)", key, value);
+    if (apply_option(h, key, value)) return fail(h, "imx_set_option: unknown option or value '%s' = '%s' (mfma = x3|f32, latency_forms = auto|off|on|unfused, conv = wino|wino_h|wino32|direct, gnn_tail = auto|fused|bf16x3|unfused, attention = auto|f16x2|bf16x3, linear = auto|f16x2|bf16x3, attention_qblocks = auto|1|2, conv_swizzle = on|off, qkv_amax = epilogue|kernel, sinkhorn_group = auto|1|2|4, sinkhorn_prefetch = auto|off|on, sinkhorn_merge = auto|kernel|fused, keypoints = auto|dense|bits, ha_masks = stored|recompute, debug_poison = off|nan|huge|zero)", key, value);
     return 0;
   });
 }
@@ -1776,6 +1891,7 @@ const char* imx_get_option(imx_handle_t h, const char* key) {
     else if (k == "attention_qblocks") h->opt_text = o.attention_qblocks < 0 ? std::string("auto") : std::to_string(o.attention_qblocks);
     else if (k == "linear") h->opt_text = o.linear < 0 ? "auto" : o.linear ? "f16x2" : "bf16x3";
     else if (k == "conv_swizzle") h->opt_text = o.conv_swizzle ? "on" : "off";
+    else if (k == "ha_masks") h->opt_text = o.ha_masks ? "recompute" : "stored";
     else if (k == "qkv_amax") h->opt_text = o.qkv_amax ? "kernel" : "epilogue";
     else if (k == "sinkhorn_group") h->opt_text = o.sinkhorn_group ? std::to_string(o.sinkhorn_group) : std::string("auto");
     else if (k == "sinkhorn_prefetch") h->opt_text = o.sinkhorn_prefetch < 0 ? "auto" : o.sinkhorn_prefetch ? "on" : "off";

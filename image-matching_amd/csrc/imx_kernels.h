@@ -34,6 +34,8 @@ struct Options {
   int attention_qblocks = -1;  // "attention_qblocks": -1 = "auto" (2 where the padded keypoint count is a multiple of 256 and one block per wave would
                                //         still leave >= 1024 workgroups -- two per slot of the chip --, else 1) | 1 | 2: 32-query blocks per wave of the
                                //         two-plane attention at head dim 32 (attention_h2q2_kernel; bit-identical results)
+  int ha_masks = 0;        // "ha_masks": 0 = "stored" (imx_homography_adapt's warp launch writes the N valid masks, the combine reads them), 1 = "recompute"
+                           //         (the combine re-evaluates them from the warp matrices; bit-identical; with debug on the masks are stored for the tap)
   int linear = -1;         // "linear": -1 = "auto" = 1 = "f16x2" (gemm_h2: the GNN's plain linear layers -- q|k|v, mlp.0', mlp.3, final_proj where the
                            //         layer tail is not fused -- as three fp16 plane products, scaled by the operands' actual (side, pair) maxima; needs
                            //         "attention" = f16x2 and weights inside the spread guard), 0 = "bf16x3" (gemm_x3: six bf16 plane products)
@@ -377,5 +379,30 @@ struct KnnArgs {
 };
 hipError_t launch_rownorm2(const float* x, int d, long rows, float* out, hipStream_t s);
 hipError_t launch_knn2(const KnnArgs& a, hipStream_t s);
+
+// ---------------------------------------------------------------- homographic adaptation (homoadapt.hip)
+// inv_warp_image_batch (utils/utils.py:388-421): dst[b] = grid_sample(src[b], M_b . normalised pixel grid), align_corners, zero padding,
+// bilinear or nearest.  src_stride = floats between the N sources (0: one source shared by all N); src null = an all-ones image.
+// mask_out (optional, (N,H,W)): compute_valid_mask of the same matrices (the in-bounds predicate of the nearest sample).  dst may be
+// null when only the mask is wanted.  H, W >= 2, N <= 65535.
+hipError_t launch_ha_warp(const float* src, long src_stride, const float* mats, int N, int H, int W, int nearest, float* dst,
+                          float* mask_out, hipStream_t s);
+// combine_heatmap (utils/utils.py:507-518) fused: out = sum_i sample(heat_i mask_i) / sum_i sample(mask_i) under unwarp_i, i ascending;
+// count (optional) = the denominator.  mask null: the masks are re-evaluated from `warp` (N,3,3), the matrices the views were warped by
+hipError_t launch_ha_combine(const float* heat, const float* mask, const float* warp, const float* unwarp, int N, int H, int W, float* out,
+                             float* count, hipStream_t s);
+// getPtsFromHeatmap (utils/utils.py:250-271): threshold (>=), exact greedy NMS (Chebyshev radius nms_dist), border removal after the
+// NMS, rows (x, y, conf) by descending conf (ties: lower row-major index first), optional 5x5 centroid refinement and top-k.
+// kHeatmapPointsRounds launches of the parallel round, then an unbounded single-workgroup pass for whatever they left undecided.
+constexpr int kHeatmapPointsRounds = 8;
+struct HeatmapPointsArgs {
+  const float* heatmap; int H, W;
+  float conf_thresh; int nms_dist; int border; int top_k; int subpixel;
+  float* pts; int cap;       // (cap,3); rows past cap are dropped
+  int* count;                // the number of points (after top_k), whatever cap is; may be null
+  void* scratch;             // heatmap_points_scratch_bytes(H, W)
+};
+size_t heatmap_points_scratch_bytes(int H, int W);
+hipError_t launch_heatmap_points(const HeatmapPointsArgs& a, hipStream_t s);
 
 }  // namespace imx

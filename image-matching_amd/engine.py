@@ -317,6 +317,93 @@ class Engine:
         self._check(self.lib.imx_op_nms(self.handle, _ptr(scores), _ptr(out), B, H, W, int(radius), _stream(self.device)))
         return out
 
+    # ------------------------------------------------------------------ homographic adaptation (pseudo-label export)
+    def _f32(self, t, shape, what):
+        if not isinstance(t, torch.Tensor):
+            t = torch.as_tensor(np.asarray(t, dtype=np.float32))
+        t = t.to(self.device, torch.float32).contiguous()
+        if tuple(t.shape) != tuple(shape):
+            raise ImxError(f"{what}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+        return t
+
+    def warp_homography(self, src, mats, mode="bilinear"):
+        """inv_warp_image_batch (utils/utils.py:388-421).  src (N,H,W), or (H,W) shared by all N matrices, or a (H, W) pair of
+        ints = an all-ones image (mode 'nearest': compute_valid_mask); mats (N,3,3).  Returns (N,H,W) float32."""
+        if mode not in ("bilinear", "nearest"):
+            raise ImxError(f"warp_homography: mode must be 'bilinear' or 'nearest', got {mode!r}")
+        N = int(mats.shape[0])
+        mats = self._f32(mats, (N, 3, 3), "warp_homography: mats")
+        if isinstance(src, (tuple, list)):
+            (H, W), img, shared = (int(v) for v in src), None, 1
+        else:
+            shared = int(src.dim() == 2)
+            H, W = int(src.shape[-2]), int(src.shape[-1])
+            img = self._f32(src, (H, W) if shared else (N, H, W), "warp_homography: src")
+        dst = torch.empty(N, H, W, dtype=torch.float32, device=self.device)
+        self._check(self.lib.imx_warp_homography(self.handle, _ptr(img), shared, N, H, W, _ptr(mats), int(mode == "nearest"),
+                                                 _ptr(dst), _stream(self.device)))
+        return dst
+
+    def combine_heatmap(self, heat, mask, unwarp, want_count=False):
+        """combine_heatmap (utils/utils.py:507-518), fused.  heat, mask (N,H,W); unwarp (N,3,3).  Returns the (H,W) map
+        [, the (H,W) sum of the un-warped masks]."""
+        N, H, W = (int(v) for v in heat.shape)
+        heat = self._f32(heat, (N, H, W), "combine_heatmap: heat")
+        mask = self._f32(mask, (N, H, W), "combine_heatmap: mask")
+        unwarp = self._f32(unwarp, (N, 3, 3), "combine_heatmap: unwarp")
+        out = torch.empty(H, W, dtype=torch.float32, device=self.device)
+        cnt = torch.empty(H, W, dtype=torch.float32, device=self.device) if want_count else None
+        self._check(self.lib.imx_combine_heatmap(self.handle, _ptr(heat), _ptr(mask), _ptr(unwarp), N, H, W, _ptr(out), _ptr(cnt),
+                                                 _stream(self.device)))
+        return (out, cnt) if want_count else out
+
+    def superpoint_heatmap(self, x):
+        """x (B,1,H,W) -> detector heatmaps (B,1,H,W): the dense SuperPoint's `semi` through flattenDetection
+        (model_wrap.py:283-309 with onlyHeatmap); the descriptor head is not run."""
+        x = self._image(x)
+        B, _, H, W = x.shape
+        heat = torch.empty(B, 1, H, W, dtype=torch.float32, device=self.device)
+        self._check(self.lib.imx_superpoint_heatmap(self.handle, _ptr(x), B, H, W, _ptr(heat), _stream(self.device)))
+        return heat
+
+    def homography_adapt(self, img, warp, unwarp, want_count=False):
+        """superpoint_export_pseudo.py:58-79 for one image (H,W): warp (N,3,3) are the matrices the image is warped by (the
+        dataset's inv_homographies), unwarp (N,3,3) the ones the heatmaps come back by (its homographies).  Returns the
+        aggregated (H,W) heatmap [, the count map]."""
+        H, W = int(img.shape[-2]), int(img.shape[-1])
+        N = int(warp.shape[0])
+        img = self._f32(img.reshape(H, W) if isinstance(img, torch.Tensor) else img, (H, W), "homography_adapt: img")
+        warp = self._f32(warp, (N, 3, 3), "homography_adapt: warp")
+        unwarp = self._f32(unwarp, (N, 3, 3), "homography_adapt: unwarp")
+        out = torch.empty(H, W, dtype=torch.float32, device=self.device)
+        cnt = torch.empty(H, W, dtype=torch.float32, device=self.device) if want_count else None
+        self._check(self.lib.imx_homography_adapt(self.handle, _ptr(img), H, W, N, _ptr(warp), _ptr(unwarp), _ptr(out), _ptr(cnt),
+                                                  _stream(self.device)))
+        return (out, cnt) if want_count else out
+
+    def heatmap_points(self, heatmap, conf_thresh, nms_dist, top_k=0, subpixel=False, cap=None):
+        """getPtsFromHeatmap (+ soft_argmax_points, top_k) on a (H,W) map, no host sync: returns (pts (cap,3) rows (x, y, conf)
+        by descending conf, count (1) int32).  count is the number of points whatever cap is; rows past min(count, cap) are
+        unwritten.  cap defaults to top_k if > 0, else to the most survivors a map of this size can have."""
+        H, W = int(heatmap.shape[-2]), int(heatmap.shape[-1])
+        heatmap = self._f32(heatmap.reshape(H, W) if isinstance(heatmap, torch.Tensor) else heatmap, (H, W), "heatmap_points: heatmap")
+        if cap is None:
+            r = max(int(nms_dist), 0) + 1
+            cap = int(top_k) if top_k and top_k > 0 else -(-H // r) * -(-W // r)
+        # one buffer: the rows, then the count word -- heatmap_points_host copies both in one transfer
+        buf = torch.empty(int(cap) * 3 + 1, dtype=torch.float32, device=self.device)
+        pts, cnt = buf[:int(cap) * 3].view(int(cap), 3), buf[int(cap) * 3:].view(torch.int32)
+        self._check(self.lib.imx_heatmap_points(self.handle, _ptr(heatmap), H, W, float(conf_thresh), int(nms_dist), int(top_k or 0),
+                                                int(bool(subpixel)), _ptr(pts), int(cap), _ptr(cnt), _stream(self.device)))
+        return pts, cnt
+
+    def heatmap_points_host(self, heatmap, conf_thresh, nms_dist, top_k=0, subpixel=False):
+        """heatmap_points, then ONE device-to-host copy (a synchronisation): the (K,3) float32 numpy rows (x, y, conf)."""
+        pts, cnt = self.heatmap_points(heatmap, conf_thresh, nms_dist, top_k=top_k, subpixel=subpixel)
+        rows = pts._base.cpu().numpy()                    # pts and cnt are views of one buffer: rows, then the count word
+        k = min(int(rows[-1:].view(np.int32)[0]), pts.shape[0])
+        return rows[:-1].reshape(-1, 3)[:k].copy()
+
     # ------------------------------------------------------------------ kernel-form options (include/imx.h: imx_set_option)
     def set_option(self, key, value):
         """'mfma' = 'x3' | 'f32', 'latency_forms' = 'auto' | 'off' | 'on' | 'unfused', 'conv' = 'wino' | 'wino_h' | 'wino32' | 'direct',

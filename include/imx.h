@@ -198,6 +198,39 @@ IMX_API int imx_warp_affine_u8(imx_handle_t h, const uint8_t* src_dev, int Hs, i
 IMX_API int imx_op_nms(imx_handle_t h, const float* scores_dev, float* out_dev, int B, int H, int W,
                int radius, void* stream);
 
+/* Homographic adaptation (pseudo-label export, superpoint_export_pseudo.py:57-110).  Matrices are (N,3,3) fp32 row-major and act
+ * on [-1,1]^2 coordinates: pixel (y, x) is (linspace(-1,1,W)[x], linspace(-1,1,H)[y]).  The caller passes both stacks (the
+ * reference's dataset inverts them in fp32, datasets/ALLSS.py:162-166); the library inverts nothing.
+ *
+ * imx_warp_homography: inv_warp_image_batch / compute_valid_mask (utils/utils.py:388-454): dst[b] = grid_sample(src[b], M_b . grid,
+ * align_corners=True, zero padding), bilinear or nearest (round half to even).  src_dev (N,H,W), or (H,W) shared by all N when
+ * src_shared; src_dev NULL = an all-ones image (nearest: the valid mask, erosion_radius 0).  dst_dev (N,H,W). */
+IMX_API int imx_warp_homography(imx_handle_t h, const float* src_dev, int src_shared, int N, int H, int W,
+                                const float* mats_dev, int nearest, float* dst_dev, void* stream);
+/* combine_heatmap (utils/utils.py:507-518) on caller-supplied heatmaps and masks (both (N,H,W)), one kernel: for every pixel
+ * out = sum_i sample(heat_i mask_i) / sum_i sample(mask_i) under unwarp_i, summed in ascending i.  A pixel no map covers is
+ * 0 / 0 = NaN, as in the reference.  count_dev (may be NULL) receives the denominator. */
+IMX_API int imx_combine_heatmap(imx_handle_t h, const float* heat_dev, const float* mask_dev, const float* unwarp_dev,
+                                int N, int H, int W, float* out_dev, float* count_dev, void* stream);
+/* SuperPointFrontend_torch.run(..., onlyHeatmap=True) (superpoint/models/model_wrap.py:283-309): the detector head of the dense
+ * SuperPoint on img_dev (B,H,W) (the descriptor head is not run), then flattenDetection (utils/utils.py:491-505): softmax over
+ * the 65 channels, dustbin dropped, depth-to-space 8 -> heat_dev (B,H,W).  H and W must be multiples of 8. */
+IMX_API int imx_superpoint_heatmap(imx_handle_t h, const float* img_dev, int B, int H, int W, float* heat_dev, void* stream);
+/* One image through superpoint_export_pseudo.py:58-79: N warps of img_dev (H,W) by warp_dev (the dataset's inv_homographies),
+ * their valid masks, the detector head of SuperPoint on all N (the descriptor head is not run), heatmaps (flattenDetection,
+ * utils/utils.py:491-505), combine by unwarp_dev (the dataset's homographies) into heatmap_dev (H,W); count_dev (H,W) may be NULL.
+ * H and W must be multiples of 8.  With debug on: taps "ha_warped", "ha_mask", "ha_heat", each (N,H,W). */
+IMX_API int imx_homography_adapt(imx_handle_t h, const float* img_dev, int H, int W, int N, const float* warp_dev,
+                                 const float* unwarp_dev, float* heatmap_dev, float* count_dev, void* stream);
+/* getPtsFromHeatmap + nms_fast (utils/utils.py:250-332) [+ soft_argmax_points, model_wrap.py:146-176; top_k,
+ * superpoint_export_pseudo.py:95-99]: candidates h >= conf_thresh (NaN never), exact greedy NMS in descending score (Chebyshev
+ * radius nms_dist; equal scores: the lower row-major pixel index ranks first), a 4-pixel border removed after the NMS, rows
+ * (x, y, conf) by descending conf into pts_dev (cap,3); subpixel: x, y moved to the centroid of the 5x5 patch; top_k <= 0: all.
+ * count_dev receives the number of points (after top_k) whatever cap is: rows past cap are dropped, rows past the count are
+ * not written, and a caller that sees count > cap calls again with a larger buffer.  Asynchronous, no host read. */
+IMX_API int imx_heatmap_points(imx_handle_t h, const float* heatmap_dev, int H, int W, float conf_thresh, int nms_dist,
+                               int top_k, int subpixel, float* pts_dev, int cap, int32_t* count_dev, void* stream);
+
 /* Parity-test taps: when enabled, forwards keep copies of named intermediates
  * ("x4","semi","desc","score_map","nms","kenc","gnn<i>","mdesc","scores_in","u","v", ...).
  * imx_debug_fetch copies one to HOST (synchronises the device); shape_out gets up to 4 dims. */
@@ -263,6 +296,8 @@ IMX_API const char* imx_timing_form(imx_handle_t h, int index);
  *                           median column's largest); otherwise, and under "bf16x3", gemm_x3's six bf16 plane products;
  * A/B switches of the bit-identity tests and of tools/ (results agree bit for bit, the Sinkhorn group to 2e-6 in the potentials with
  * equal matches); none of them is read from the environment:
+ *   "ha_masks"          "stored" (default) imx_homography_adapt stores the N valid masks and the combine reads them; "recompute": the
+ *                       combine re-evaluates them from the warp matrices (bit-identical);
  *   "conv_swizzle"      "on" (default) the tensor between two pair-form 3x3 layers without a pool is tile-swizzled; "off": blocked;
  *   "qkv_amax"          "epilogue" (default) a plain q|k|v projection writes the (side, pair) maxima in its epilogue; "kernel": a separate pass;
  *   "sinkhorn_group"    "auto" (default: the most slabs per workgroup -- 4, 2 or 1 -- whose groups still fill the chip's resident
