@@ -1,4 +1,4 @@
-// imx_kernels.h — internal launch interface between the C-ABI host code (imx_api.cpp) and the
+// imx_kernels.h — internal launch interface between the host code (imx_host.h and the imx_*.cpp units) and the
 // gfx950 kernels.  Activations are fp32, channels-last: images (B,H,W,C) "NHWC", keypoint
 // features (rows, C).  See DESIGN.md for the data layout in HBM and per-kernel rooflines.
 #pragma once
@@ -42,7 +42,7 @@ struct Options {
 };
 
 // The form a launcher picked ("gemm_x3:bf16x3", "conv3x3_wino24:f32", ...: kernel family, then the matrix pipe it runs on or
-// "hbm" for streaming kernels).  Set by every launch_* that has more than one form, read by imx_api.cpp's per-launch timing so
+// "hbm" for streaming kernels).  Set by every launch_* that has more than one form, read by imx_host.h's per-launch timing (run) so
 // that imx_timing_form reports what actually ran.
 extern thread_local const char* last_form;
 
@@ -138,7 +138,7 @@ struct GemmArgs {
   unsigned long long* trace = nullptr;   // developer instrumentation (a -DGH2_TRACE build of gemm_h2.hip only): s_memtime stamps of the first workgroups' chunks
 };
 bool gemm_x3_amax_supported(const GemmArgs& a);
-// wh2 = the weights as two fp16 planes of w s in B-fragment order [Npad/32][K/16][2][64][8] (imx_api.cpp: split_f16x2)
+// wh2 = the weights as two fp16 planes of w s in B-fragment order [Npad/32][K/16][2][64][8] (imx_weights.cpp: split_f16x2)
 bool gemm_h2_supported(const GemmArgs& a);
 hipError_t launch_gemm_h2(const GemmArgs& a, const void* wh2, hipStream_t s);
 // max |x| over the valid rows of every (side, pair), rows of d floats (d % 4 == 0): what gnn_tail_h2 / gemm_h2 scale layer 0's x by
@@ -147,7 +147,7 @@ hipError_t launch_rows_amax_any(const float* x, int d, int B, int N0p, int N1p, 
 hipError_t launch_gemm(const GemmArgs& a, hipStream_t s);
 // The tail of one GNN layer for small row counts, fused (gnn_small.hip): hidden = relu([x | att] w1 + b1); x += hidden w2 + b2;
 // out = x w3 + b3 (the next layer's q|k|v, n3 = 3 d, or final_proj, n3 = d).  Weights unpadded, in B-fragment order
-// [K/16][4][N][4] (imx_api.cpp:fragment_order).
+// [K/16][4][N][4] (imx_weights.cpp:fragment_order).
 struct GnnSmallArgs {
   float* x;                             // [M][d], updated in place
   const float* att;                     // [M][d]

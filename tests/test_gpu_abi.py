@@ -180,3 +180,48 @@ def test_bad_calls_return_errors_with_messages_and_leave_the_handle_usable():
     out = eng.match_pairs(x[:1], x[1:], want_desc=True)
     torch.cuda.synchronize()
     assert int(out["counts0"][0]) == K and int((out["matches0"] >= 0).sum()) > 0
+
+
+# key -> [(canonical spelling, aliases accepted for the same value)], in the order imx_set_option's error message lists the values
+_OPTION_SPELLINGS = {
+    "mfma": [("x3", ()), ("f32", ())],
+    "latency_forms": [("auto", ()), ("off", ("0",)), ("on", ("1",)), ("unfused", ())],
+    "conv": [("wino", ()), ("wino_h", ()), ("wino32", ("wx3",)), ("direct", ())],
+    "gnn_tail": [("auto", ()), ("fused", ("1",)), ("bf16x3", ()), ("unfused", ("0",))],
+    "attention": [("auto", ()), ("f16x2", ("1",)), ("bf16x3", ("x3", "0"))],
+    "linear": [("auto", ()), ("f16x2", ("1",)), ("bf16x3", ("x3", "0"))],
+    "attention_qblocks": [("auto", ()), ("1", ()), ("2", ())],
+    "conv_swizzle": [("on", ("1",)), ("off", ("0",))],
+    "qkv_amax": [("epilogue", ()), ("kernel", ())],
+    "sinkhorn_group": [("auto", ("0",)), ("1", ()), ("2", ()), ("4", ())],
+    "sinkhorn_prefetch": [("auto", ()), ("off", ("0",)), ("on", ("1",))],
+    "sinkhorn_merge": [("auto", ()), ("kernel", ()), ("fused", ())],
+    "keypoints": [("auto", ()), ("dense", ()), ("bits", ())],
+    "ha_masks": [("stored", ()), ("recompute", ())],
+    "debug_poison": [("off", ()), ("nan", ()), ("huge", ()), ("zero", ())],
+}
+
+
+def test_every_option_spelling_round_trips_and_bad_values_change_nothing():
+    """imx_set_option then imx_get_option, for every key and every accepted spelling (the table of imx_options.cpp): the answer is the
+    canonical spelling.  A value the key does not have returns -1, leaves the option as it was, and the message lists that key's
+    values; the read-only arith_guard cannot be set.  No kernel runs (a fresh handle has no workspaces for debug_poison to fill)."""
+    from image_matching_amd.engine import Engine
+    eng = Engine(util.sp_config(128, 50), util.sg_config(128), "cuda")
+    lib, h = eng.lib, eng.handle
+    get = lambda k: lib.imx_get_option(h, k.encode()).decode()
+    for key, values in _OPTION_SPELLINGS.items():
+        for canonical, aliases in values:
+            for text in (canonical,) + aliases:
+                assert lib.imx_set_option(h, key.encode(), text.encode()) == 0, (key, text, lib.imx_last_error(h).decode())
+                assert get(key) == canonical, (key, text, get(key))
+                for bad in ("", "no_such_value", canonical.upper() + "_", "3", "-1"):
+                    assert lib.imx_set_option(h, key.encode(), bad.encode()) == -1, (key, bad)
+                    assert get(key) == canonical, (key, bad, get(key))
+                    msg = lib.imx_last_error(h).decode()
+                    assert f"{key} = {'|'.join(v for v, _ in values)}" in msg and f"'{key}' = '{bad}'" in msg, msg
+        assert lib.imx_set_option(h, key.encode(), values[0][0].encode()) == 0
+    guard = get("arith_guard")
+    assert guard.startswith("conv: max spread")
+    for text in ("", "f16x2", guard):
+        assert lib.imx_set_option(h, b"arith_guard", text.encode()) == -1 and get("arith_guard") == guard

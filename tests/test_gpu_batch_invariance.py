@@ -165,7 +165,7 @@ GUARD_LAYER, FLAT_CH, FLAT_A, V_GAIN = 5, 17, 2.0 ** 8, 2.0 ** 4
 
 
 def _guards(sd, l, d):
-    """Host restatement of the two weights-derived guards on layer l's q|k|v (imx_api.cpp): the attention's -- per projection,
+    """Host restatement of the two weights-derived guards on layer l's q|k|v (imx_host.h: attn_f16x2_ok, gemm_h2_weights_ok): the attention's -- per projection,
     largest / median column L2 norm -- and the linear layers' (split_f16x2) -- largest |w| / median column maximum over q|k|v."""
     Ws = [np.asarray(sd[f"gnn.layers.{l}.attn.proj.{w}.weight"], np.float64) for w in range(3)]
     att = max(np.sqrt((w ** 2).sum(1)).max() / np.sort(np.sqrt((w ** 2).sum(1)))[d // 2] for w in Ws)

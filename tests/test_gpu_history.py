@@ -4,7 +4,7 @@ current call (padded tiles of the swizzled tensors, the short last slice's maxim
 past the count, candidate buffers past an image's yield).  On a fresh handle those regions are usually zero, so a read that should
 have been masked is invisible.  Every test here compares a used or poisoned handle ("debug_poison": include/imx.h) with THE SAME CALL
 ON A FRESH HANDLE, bit for bit, on every output and on the valid region of the taps.  Nothing here provokes a fault: the hook writes
-values into float workspaces only (imx_api.cpp: poisonable()).  Needs an MI355X.
+values into float workspaces only (imx_host.h: poisonable()).  Needs an MI355X.
 Wall time on an MI355X: 22 s alone (tests/test_gpu_padding.py: 14 s); the whole GPU suite with both 540 s, about 505 s without them."""
 import numpy as np
 import pytest

@@ -273,7 +273,7 @@ def test_fp16_plane_convolutions_on_inputs_that_stress_their_scales(reps):
 
 def test_an_image_of_a_260_image_batch_equals_the_same_image_alone():
     """The per-image maxima behind the fp16 scales live in 256 slots per layer: a batch of more than 256 images runs its 3x3 layers in
-    slices of 256 images with separate tables (imx_api.cpp), so an image's scales never depend on which other images share the call --
+    slices of 256 images with separate tables (imx_superpoint.cpp: sp_detect), so an image's scales never depend on which other images share the call --
     image b of a 260-image batch is BIT-IDENTICAL to the same image in a call of its own (different kernels run: the batch takes the
     tile-pair form, the single image the tile-per-workgroup form, which agree bit for bit)."""
     from image_matching_amd import _lib as L

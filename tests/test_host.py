@@ -244,7 +244,7 @@ def test_superglue_checkpoint_formats(tmp_path):
 
 def test_winograd_f2x4_matrices_reproduce_the_direct_convolution():
     """The 3x3 layers run as Winograd F(2x4,3x3) (conv1ab_wino24.hip, conv3x3_wino24.hip; U = G2 g G4^T is built in
-    imx_api.cpp).  The transform matrices those files use must satisfy  Y = A2^T [(G2 g G4^T) (.) (B2^T d B4)] A4  ==  the
+    wino24_pack.h).  The transform matrices those files use must satisfy  Y = A2^T [(G2 g G4^T) (.) (B2^T d B4)] A4  ==  the
     direct 3x3 correlation of a 4x6 patch, exactly in float64 (F.conv2d semantics: no kernel flip)."""
     rng = np.random.default_rng(0)
     BT2 = np.array([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]], dtype=np.float64)
@@ -368,16 +368,20 @@ def test_heavy_weight_sets_are_function_preserving():
 
 
 def test_every_handle_option_is_documented():
-    """Every key imx_set_option accepts (the chain of `key == "..."` in imx_api.cpp's apply_option) and the read-only ones appear in
-    include/imx.h's option documentation and in INTEGRATION.md -- a switch that changes which kernels run must not be findable only in
-    the source (undocumented behaviour changes)."""
+    """Every key imx_set_option accepts (the rows of kOptionTable in imx_options.cpp, the one place a key is spelled) and the read-only
+    ones appear in include/imx.h's option documentation and in INTEGRATION.md -- a switch that changes which kernels run must not be
+    findable only in the source (undocumented behaviour changes).  The key set itself is pinned: adding or dropping an
+    option is a change of the interface."""
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = open(os.path.join(root, "image-matching_amd", "csrc", "imx_api.cpp")).read()
-    body = src[src.index("int apply_option("):]
-    body = body[:body.index("\n}\n")]
-    keys = sorted(set(re.findall(r'key == "([a-z_0-9]+)"', body)))
-    assert len(keys) >= 12, keys
+    src = open(os.path.join(root, "image-matching_amd", "csrc", "imx_options.cpp")).read()
+    body = src[src.index("const OptionRow kOptionTable[] = {"):]
+    body = body[:body.index("\n};\n")]
+    keys = re.findall(r'^  \{"([a-z_0-9]+)", ', body, re.M)
+    assert len(keys) == len(set(keys)), keys
+    assert sorted(keys) == sorted(["mfma", "latency_forms", "gnn_tail", "attention", "conv", "attention_qblocks", "linear", "ha_masks",
+                                   "conv_swizzle", "qkv_amax", "sinkhorn_group", "sinkhorn_merge", "keypoints", "sinkhorn_prefetch",
+                                   "debug_poison"]), keys
     header = open(os.path.join(root, "include", "imx.h")).read()
     integ = open(os.path.join(root, "INTEGRATION.md")).read()
     for k in keys + ["arith_guard"]:

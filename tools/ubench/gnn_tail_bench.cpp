@@ -15,7 +15,7 @@ using namespace imx;
 namespace imx { void gnn_tail_trace_dump(); }
 #endif
 namespace imx { thread_local const char* last_form = nullptr; }
-static std::vector<uint16_t> x3_planes(const std::vector<float>& w, int K, int N) {      // gemm_x3's B-fragment order (imx_api.cpp: split_bf16x3)
+static std::vector<uint16_t> x3_planes(const std::vector<float>& w, int K, int N) {      // gemm_x3's B-fragment order (imx_weights.cpp: split_bf16x3)
   const int nst = K / 16;
   std::vector<uint16_t> pl((size_t)3 * N * K);
   for (int k = 0; k < K; ++k)

@@ -15,7 +15,7 @@ from tests import util  # noqa: E402
 
 torch.set_grad_enabled(False)
 
-# F(2,3) and F(4,3) (points 0, +-1, +-2, inf; the matrices of csrc/imx_api.cpp:wino24_transform and wino24_pk.h)
+# F(2,3) and F(4,3) (points 0, +-1, +-2, inf; the matrices of csrc/wino24_pack.h:wino24_transform and wino24_pk.h)
 BT = {2: np.array([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]], np.float64),
       4: np.array([[4, 0, -5, 0, 1, 0], [0, -4, -4, 1, 1, 0], [0, 4, -4, -1, 1, 0], [0, -2, -1, 2, 1, 0], [0, 2, -1, -2, 1, 0],
                    [0, 4, 0, -5, 0, 1]], np.float64)}
