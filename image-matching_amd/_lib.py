@@ -15,7 +15,8 @@ EXPORTS = (
     "imx_create", "imx_destroy", "imx_last_error", "imx_load_weight", "imx_finalize_weights",
     "imx_superpoint_detect", "imx_superpoint_describe", "imx_superpoint_dense", "imx_superglue_forward",
     "imx_match_pairs", "imx_pack_records", "imx_gather_records", "imx_estimate_affine_partial", "imx_knn_ratio_match", "imx_ingest_resize_u8", "imx_warp_affine_u8", "imx_op_nms",
-    "imx_warp_homography", "imx_combine_heatmap", "imx_superpoint_heatmap", "imx_homography_adapt", "imx_heatmap_points", "imx_set_debug", "imx_debug_fetch", "imx_set_timing",
+    "imx_warp_homography", "imx_combine_heatmap", "imx_superpoint_heatmap", "imx_homography_adapt", "imx_heatmap_points",
+    "imx_warp_perspective_u8", "imx_gt_matches", "imx_match_loss", "imx_set_debug", "imx_debug_fetch", "imx_set_timing",
     "imx_timing_report", "imx_timing_reset", "imx_timing_form", "imx_set_option", "imx_get_option", "imx_version",
 )
 
@@ -83,6 +84,9 @@ def load_library():
     lib.imx_superpoint_heatmap.argtypes = [vp, f32p, i32, i32, i32, f32p, vp]
     lib.imx_homography_adapt.argtypes = [vp, f32p, i32, i32, i32, f32p, f32p, f32p, f32p, vp]
     lib.imx_heatmap_points.argtypes = [vp, f32p, i32, i32, ctypes.c_float, i32, i32, i32, f32p, i32, vp, vp]
+    lib.imx_warp_perspective_u8.argtypes = [vp, vp, i64, vp, vp, i32, i32, i32, vp]
+    lib.imx_gt_matches.argtypes = [vp, i32, f32p, vp, i32, f32p, vp, i32, vp, ctypes.c_double, f32p, vp, vp, vp, vp, vp, vp]
+    lib.imx_match_loss.argtypes = [vp, i32, vp, vp, i32, vp, vp, f32p, vp, vp]
     lib.imx_set_debug.argtypes = [vp, i32]
     lib.imx_debug_fetch.argtypes = [vp, ctypes.c_char_p, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i32)]
     lib.imx_set_timing.argtypes = [vp, i32]

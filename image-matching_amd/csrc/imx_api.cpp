@@ -1,5 +1,6 @@
 // imx_api.cpp -- C ABI of libimx.so (include/imx.h): the entry points, each a guard around argument checks and the stage functions of
-// imx_host.h (weights: imx_weights.cpp; launch sequences: imx_superpoint.cpp, imx_superglue.cpp; options: imx_options.cpp), plus the
+// imx_host.h (weights: imx_weights.cpp; launch sequences: imx_superpoint.cpp, imx_superglue.cpp; options: imx_options.cpp; the training-pair
+// entry points live in imx_trainpairs.cpp), plus the
 // RCCL loader, the debug-tap fetch and the timing report.  All arithmetic of the path runs in the kernels declared in imx_kernels.h.
 #include "imx_host.h"
 
@@ -13,15 +14,6 @@ thread_local const char* last_form = nullptr;
 }
 
 namespace {
-// an entry point that works on the handle's device: guarded(), a null handle is an error, the device is made current
-template <class F>
-int on_device(imx_handle_t h, const char* where, F&& f) noexcept {
-  return guarded(h, where, [&]() -> int {
-    if (!h) return -1;
-    HIP_OK(h, hipSetDevice(h->device));
-    return f();
-  });
-}
 bool ends_with(const std::string& s, const std::string& suf) {
   return s.size() >= suf.size() && s.compare(s.size() - suf.size(), suf.size(), suf) == 0;
 }
@@ -167,7 +159,8 @@ int imx_superglue_forward(imx_handle_t h, int B, const float* kpts0_dev, const f
   return on_device(h, "imx_superglue_forward", [&]() -> int {
     SgSide sd[2] = {{kpts0_dev, scores0_dev, desc0_dev, desc0_stride_b, desc0_stride_c, desc0_stride_n, n0_dev, N0, H0, W0},
                     {kpts1_dev, scores1_dev, desc1_dev, desc1_stride_b, desc1_stride_c, desc1_stride_n, n1_dev, N1, H1, W1}};
-    return sg_forward(h, B, sd, matches0_dev, matches1_dev, mscores0_dev, mscores1_dev, as_stream(stream));
+    if (sg_forward(h, B, sd, matches0_dev, matches1_dev, mscores0_dev, mscores1_dev, as_stream(stream))) return -1;
+    return sg_keep_counts(h, B, n0_dev, n1_dev, as_stream(stream));
   });
 }
 
@@ -186,7 +179,8 @@ int imx_match_pairs(imx_handle_t h, const float* img0_dev, const float* img1_dev
     if (sp_describe(h, 0, 2 * B, K, kpts0_dev, scores0_dev, desc0_dev, s, B, kpts1_dev, scores1_dev, desc1_dev)) return -1;   // both sides, one launch
     SgSide sd[2] = {{kpts0_dev, scores0_dev, desc0_dev, (int64_t)K * d, 1, d, counts, K, H, W},
                     {kpts1_dev, scores1_dev, desc1_dev, (int64_t)K * d, 1, d, counts + B, K, H, W}};
-    return sg_forward(h, B, sd, matches0_dev, matches1_dev, mscores0_dev, mscores1_dev, s);
+    if (sg_forward(h, B, sd, matches0_dev, matches1_dev, mscores0_dev, mscores1_dev, s)) return -1;
+    return sg_keep_counts(h, B, counts, counts + B, s);       // (mp.counts is the handle's own: nothing is copied)
   });
 }
 

@@ -1,5 +1,5 @@
 // imx_host.h -- internal header of the host units of libimx.so (imx_api.cpp, imx_options.cpp, imx_weights.cpp, imx_superpoint.cpp,
-// imx_superglue.cpp): the handle, its weight sets and workspaces, the launch helpers, the weights-derived guards of the fp16-plane
+// imx_superglue.cpp, imx_trainpairs.cpp): the handle, its weight sets and workspaces, the launch helpers, the weights-derived guards of the fp16-plane
 // forms, and the stage functions the entry points call.  Nothing here is exported (hidden visibility; imx.map).
 #pragma once
 #include "../../include/imx.h"
@@ -106,6 +106,10 @@ struct imx_handle_s {
   float bin_score = 1.f;
   // workspace
   std::map<std::string, DevBuf> bufs;
+  // what the last SuperGlue forward left in the workspace, for imx_match_loss: valid only once the entry point has put the counts
+  // somewhere that outlives the call (sg_keep_counts); withdrawn wherever one of these buffers is freed or overwritten
+  struct { bool valid = false; int B = 0, N0 = 0, N1 = 0, N0p = 0, N1p = 0; const float *S = nullptr, *u = nullptr, *v = nullptr;
+           const int32_t *n0 = nullptr, *n1 = nullptr; float alpha = 1.f; } sg_last;
   // state of the last detect
   int det_B = 0, det_H = 0, det_W = 0, det_Hc = 0, det_Wc = 0, det_Ksel = 0;
   // kernel-form options (imx_set_option; the environment only seeds them at imx_create)
@@ -166,6 +170,8 @@ inline float* ws(imx_handle_t h, const std::string& name, size_t bytes) {
     // the lazily materialised "nms" tap, whose inputs it may be
     for (auto it = h->taps.begin(); it != h->taps.end();) it = inside(it->second.p, b) ? h->taps.erase(it) : std::next(it);
     if (inside(h->nms_lazy.smap, b) || inside(h->nms_lazy.nms, b) || inside(h->nms_lazy.scratch, b)) h->nms_lazy.pending = false;
+    // ... and what imx_match_loss would read of the last SuperGlue forward
+    if (inside(h->sg_last.S, b) || inside(h->sg_last.u, b) || inside(h->sg_last.v, b) || inside(h->sg_last.n0, b) || inside(h->sg_last.n1, b)) h->sg_last.valid = false;
     (void)hipDeviceSynchronize();
     (void)hipFree(b.p);
     b.p = nullptr;
@@ -236,6 +242,16 @@ int guarded(imx_handle_t h, const char* where, F&& f) noexcept {
   }
 }
 
+// an entry point that works on the handle's device: guarded(), a null handle is an error, the device is made current
+template <class F>
+int on_device(imx_handle_t h, const char* where, F&& f) noexcept {
+  return guarded(h, where, [&]() -> int {
+    if (!h) return -1;
+    HIP_OK(h, hipSetDevice(h->device));
+    return f();
+  });
+}
+
 inline hipStream_t as_stream(void* s) { return static_cast<hipStream_t>(s); }
 inline int pad32(int n) { return ((n + 31) / 32) * 32; }
 
@@ -301,6 +317,11 @@ struct GemmExtra {
 };
 int gemm(imx_handle_t h, hipStream_t s, const char* name, const GemmW& W, const float* a0, int lda0, int K0, const float* a1,
          int lda1, int K1, const float* res, int ldr, float* out, int ldo, int M, bool relu, GemmExtra* ex = nullptr);
+
+// imx_trainpairs.cpp
+// after sg_forward, by the entry point that called it: keeps the per-pair counts of that forward where imx_match_loss can read them later
+// (the caller's count tensors are borrowed for the call only) and marks the forward's score matrix and potentials as readable
+int sg_keep_counts(imx_handle_t h, int B, const int32_t* n0, const int32_t* n1, hipStream_t s);
 
 // imx_options.cpp
 int apply_option(imx_handle_t h, const std::string& key, const std::string& v);   // 0, or -1 for an unknown key / value

@@ -405,4 +405,34 @@ struct HeatmapPointsArgs {
 size_t heatmap_points_scratch_bytes(int H, int W);
 hipError_t launch_heatmap_points(const HeatmapPointsArgs& a, hipStream_t s);
 
+// ---------------------------------------------------------------- SuperGlue training pairs (trainpairs.hip)
+// cv2.warpPerspective(uint8, INTER_LINEAR, constant border 0) of B images, each by its own INVERSE matrix minv (B,3,3) double (device)
+hipError_t launch_warp_perspective_u8(const uint8_t* src, long sstride, const double* minv, uint8_t* dst, int B, int H, int W, hipStream_t s);
+// datasets/GlueSparse.py:64-82 for B pairs: projection, the nearest neighbour of every point in either direction, the mutual test and
+// the columns of all_matches.  proj / nn0 / nn1 / d0 are scratch; the outputs are written for every row and column (-1 past the counts).
+struct GtArgs {
+  const float* kpts0; const float* kpts1;   // (B,N0,2) / (B,N1,2) (x,y); rows past the counts are never read
+  const int* n0; const int* n1;             // (B) counts, or null = N0 / N1
+  const double* m;                          // (B,3,3) forward matrices
+  double radius;
+  int B, N0, N1;
+  float* proj; float* proj_out;             // (B,N0,2) scratch; the caller's copy (may be null)
+  int* nn0; int* nn1; double* d0;           // (B,N0) / (B,N1) / (B,N0) scratch
+  long long* gt0; long long* gt1;           // (B,N0) / (B,N1)
+  long long* all_matches;                   // (B,2,N0+N1)
+  int* n_matches; int* n_all;               // (B)
+};
+hipError_t launch_gt_matches(const GtArgs& a, hipStream_t s);
+// superglue_train.py:289-299 on the score matrix and potentials a SuperGlue forward left: loss (B); stats (B,3) or null
+struct LossArgs {
+  const float* S; const float* u; const float* v;   // (B,N0p,N1p), (B,N0p+1), (B,N1p+1)
+  const int* n0; const int* n1;                     // (B) counts of that forward, or null = N0 / N1
+  int B, N0, N1, N0p, N1p;
+  float alpha;                                      // bin_score
+  const long long* all_matches; const int* n_all; int L;   // (B,2,L), (B)
+  const long long* matches0; const long long* gt0;  // (B,N0); read only when stats is given
+  float* loss; int* stats;
+};
+hipError_t launch_match_loss(const LossArgs& a, hipStream_t s);
+
 }  // namespace imx

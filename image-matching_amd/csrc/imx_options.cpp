@@ -47,6 +47,7 @@ int set_poison(imx_handle_t h, int byte) {
       if (kv.second.p && poisonable(kv.first) && hipMemset(kv.second.p, byte, kv.second.bytes) != hipSuccess) return -1;
     if (hipDeviceSynchronize() != hipSuccess) return -1;
     h->nms_lazy.pending = false;   // (its inputs are gone: the "nms" tap now reads what every other tap reads, the pattern)
+    h->sg_last.valid = false;      // (likewise the score matrix and potentials imx_match_loss would read)
   }
   h->poison = byte;
   return 0;

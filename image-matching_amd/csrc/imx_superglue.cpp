@@ -61,6 +61,8 @@ int sg_forward(imx_handle_t h, int B, const SgSide sd[2], int64_t* m0, int64_t* 
   const int N0 = sd[0].N, N1 = sd[1].N;
   if (B <= 0 || N0 < 0 || N1 < 0) return fail(h, "bad SuperGlue shapes B=%d N0=%d N1=%d", B, N0, N1);
   const size_t f = sizeof(float);
+  h->sg_last.valid = false;   // (imx_match_loss: nothing of an earlier forward is readable from here on)
+  h->sg_last.S = nullptr;
   if (N0 == 0 || N1 == 0) {   // superglue_test.py:235-242 (dtype handling is the Python side's)
     if (N0) { HIP_OK(h, hipMemsetAsync(m0, 0xFF, (size_t)B * N0 * 8, s)); HIP_OK(h, hipMemsetAsync(ms0, 0, (size_t)B * N0 * f, s)); }
     if (N1) { HIP_OK(h, hipMemsetAsync(m1, 0xFF, (size_t)B * N1 * 8, s)); HIP_OK(h, hipMemsetAsync(ms1, 0, (size_t)B * N1 * f, s)); }
@@ -306,6 +308,8 @@ int sg_forward(imx_handle_t h, int B, const SgSide sd[2], int64_t* m0, int64_t* 
   tap(h, "v", v, {B, N1p + 1});
   tap(h, "max0", max0, {B, N0p});
   tap(h, "max1", max1, {B, N1p});
+  h->sg_last.B = B; h->sg_last.N0 = N0; h->sg_last.N1 = N1; h->sg_last.N0p = N0p; h->sg_last.N1p = N1p;
+  h->sg_last.S = S; h->sg_last.u = u; h->sg_last.v = v; h->sg_last.alpha = h->bin_score;      // (readable once sg_keep_counts has run)
   return 0;
 }
 

@@ -404,6 +404,101 @@ class Engine:
         k = min(int(rows[-1:].view(np.int32)[0]), pts.shape[0])
         return rows[:-1].reshape(-1, 3)[:k].copy()
 
+    # ------------------------------------------------------------------ SuperGlue training pairs (datasets/GlueSparse.py)
+    def _matrices(self, M, B, what, invert=False):
+        """(B,3,3) float64 on the device; `invert`: each matrix inverted on the host in double first (cv2.warpPerspective's own
+        inversion; a device tensor is read back for it, so batch producers pass host matrices)."""
+        if isinstance(M, torch.Tensor) and not invert:
+            m = M.to(self.device, torch.float64).reshape(-1, 3, 3).contiguous()
+        else:
+            a = (M.detach().cpu().numpy() if isinstance(M, torch.Tensor) else np.asarray(M)).astype(np.float64).reshape(-1, 3, 3)
+            if invert:
+                a = np.stack([np.linalg.inv(x) for x in a])
+            m = torch.from_numpy(np.ascontiguousarray(a)).to(self.device, non_blocking=True)
+        if m.shape[0] != B:
+            raise ImxError(f"{what}: {m.shape[0]} matrices for a batch of {B}")
+        return m
+
+    def warp_perspective_u8(self, img_u8, M, inverse=False):
+        """cv2.warpPerspective(image, M, (W,H)) of datasets/GlueSparse.py:32 for a batch: img_u8 (B,H,W) or (H,W) uint8, M (B,3,3)
+        forward matrices (float64, host; `inverse`: M already holds the inverses).  Returns (B,H,W) uint8 on the device."""
+        if img_u8.dtype != torch.uint8:
+            raise TypeError("warp_perspective_u8 expects uint8 gray images")
+        src = img_u8.to(self.device, non_blocking=True)
+        src = (src[None] if src.dim() == 2 else src).contiguous()
+        B, H, W = src.shape
+        minv = self._matrices(M, B, "warp_perspective_u8", invert=not inverse)
+        dst = torch.empty(B, H, W, dtype=torch.uint8, device=self.device)
+        self._check(self.lib.imx_warp_perspective_u8(self.handle, _ptr(src), H * W, _ptr(minv), _ptr(dst), B, H, W, _stream(self.device)))
+        return dst
+
+    def gt_matches(self, kpts0, kpts1, M, n0=None, n1=None, radius=3.0, want_proj=False):
+        """datasets/GlueSparse.py:64-82 for B pairs, no host sync: kpts{0,1} (B,N{0,1},2) float32, M (B,3,3) forward matrices,
+        n{0,1} (B) int32 counts or None.  Returns dict: gt0 (B,N0), gt1 (B,N1), all_matches (B,2,N0+N1) int64, n_matches, n_all
+        (B) int32 [, projected (B,N0,2)]."""
+        dev = self.device
+        kpts0 = kpts0.to(dev, torch.float32).contiguous()
+        kpts1 = kpts1.to(dev, torch.float32).contiguous()
+        B, N0, N1 = kpts0.shape[0], kpts0.shape[1], kpts1.shape[1]
+        if kpts1.shape[0] != B:
+            raise ImxError("gt_matches: the two sides differ in batch size")
+        m = self._matrices(M, B, "gt_matches")
+        for n in (n0, n1):
+            if n is not None and not (n.dtype == torch.int32 and n.numel() == B and n.device == dev and n.is_contiguous()):
+                raise ImxError(f"gt_matches: counts must be contiguous int32 tensors of {B} elements on {dev}")
+        out = {"gt0": torch.empty(B, N0, dtype=torch.int64, device=dev), "gt1": torch.empty(B, N1, dtype=torch.int64, device=dev),
+               "all_matches": torch.empty(B, 2, N0 + N1, dtype=torch.int64, device=dev),
+               "n_matches": torch.empty(B, dtype=torch.int32, device=dev), "n_all": torch.empty(B, dtype=torch.int32, device=dev)}
+        if want_proj:
+            out["projected"] = torch.empty(B, N0, 2, dtype=torch.float32, device=dev)
+        self._check(self.lib.imx_gt_matches(self.handle, B, _ptr(kpts0), _ptr(n0), N0, _ptr(kpts1), _ptr(n1), N1, _ptr(m), float(radius),
+                                            _ptr(out.get("projected")), _ptr(out["gt0"]), _ptr(out["gt1"]), _ptr(out["all_matches"]),
+                                            _ptr(out["n_matches"]), _ptr(out["n_all"]), _stream(dev)))
+        return out
+
+    def match_loss(self, all_matches, n_all, matches0=None, gt0=None):
+        """The objective of superglue/models/superglue_train.py:289-299 for the pairs of the LAST superglue() / match_pairs() of this
+        engine: all_matches (B,2,L) int64, n_all (B) int32.  Returns loss (B) float32 [, stats (B,3) int32 = ground-truth, predicted
+        and correct matches, when matches0 and gt0 (B,N0) are given]."""
+        dev = self.device
+        all_matches = all_matches.to(dev, torch.int64).contiguous()
+        n_all = n_all.to(dev, torch.int32).contiguous()
+        B, _, Lc = all_matches.shape
+        if n_all.numel() != B:
+            raise ImxError(f"match_loss: {n_all.numel()} column counts for a batch of {B}")
+        loss = torch.empty(B, dtype=torch.float32, device=dev)
+        stats = None
+        if matches0 is not None and gt0 is not None:
+            matches0 = matches0.to(dev, torch.int64).contiguous()
+            gt0 = gt0.to(dev, torch.int64).contiguous()
+            if matches0.shape != gt0.shape or matches0.shape[0] != B:
+                raise ImxError(f"match_loss: matches0 {tuple(matches0.shape)} and gt0 {tuple(gt0.shape)} must both be (B,N0)")
+            stats = torch.empty(B, 3, dtype=torch.int32, device=dev)
+        self._check(self.lib.imx_match_loss(self.handle, B, _ptr(all_matches), _ptr(n_all), Lc, _ptr(matches0 if stats is not None else None),
+                                            _ptr(gt0 if stats is not None else None), _ptr(loss), _ptr(stats), _stream(dev)))
+        return (loss, stats) if stats is not None else loss
+
+    def train_pairs(self, img_u8, M, radius=3.0):
+        """B training samples of datasets/GlueSparse.py:24-104 on one stream with no host synchronisation: the warp of every image by
+        its matrix, `/255` of both stacks, SuperPoint on the 2B images (max_keypoints = K > 0) and the ground-truth assignment.
+        img_u8 (B,H,W) uint8, M (B,3,3) float64 forward matrices (host).  Returns dict of device tensors: warped (B,H,W) uint8,
+        keypoints{0,1} (B,K,2), scores{0,1} (B,K), descriptors{0,1} (B,K,d), counts{0,1} (B), and gt_matches' entries."""
+        K = self.max_keypoints
+        if K <= 0:
+            raise ImxError("train_pairs needs max_keypoints > 0")
+        src = img_u8.to(self.device, non_blocking=True).contiguous()
+        B, H, W = src.shape
+        M = (M.detach().cpu().numpy() if isinstance(M, torch.Tensor) else np.asarray(M)).astype(np.float64).reshape(-1, 3, 3)
+        warped = self.warp_perspective_u8(src, M)
+        x = torch.empty(2 * B, 1, H, W, dtype=torch.float32, device=self.device)
+        self.ingest(src, out=x[:B])
+        self.ingest(warped, out=x[B:])
+        kpts, scores, desc, counts = self.superpoint_batch(x)
+        out = {"warped": warped, "keypoints0": kpts[:B], "keypoints1": kpts[B:], "scores0": scores[:B], "scores1": scores[B:],
+               "descriptors0": desc[:B], "descriptors1": desc[B:], "counts0": counts[:B], "counts1": counts[B:]}
+        out.update(self.gt_matches(out["keypoints0"], out["keypoints1"], M, counts[:B], counts[B:], radius))
+        return out
+
     # ------------------------------------------------------------------ kernel-form options (include/imx.h: imx_set_option)
     def set_option(self, key, value):
         """'mfma' = 'x3' | 'f32', 'latency_forms' = 'auto' | 'off' | 'on' | 'unfused', 'conv' = 'wino' | 'wino_h' | 'wino32' | 'direct',

@@ -231,6 +231,36 @@ IMX_API int imx_homography_adapt(imx_handle_t h, const float* img_dev, int H, in
 IMX_API int imx_heatmap_points(imx_handle_t h, const float* heatmap_dev, int H, int W, float conf_thresh, int nms_dist,
                                int top_k, int subpixel, float* pts_dev, int cap, int32_t* count_dev, void* stream);
 
+/* SuperGlue training pairs (datasets/GlueSparse.py:24-104, superglue/models/superglue_train.py:289-299).  Asynchronous, no host read.
+ *
+ * imx_warp_perspective_u8: cv2.warpPerspective(image, M, (W,H)) of GlueSparse.py:32 for B images, one matrix each: INTER_LINEAR,
+ * constant border 0.  minv_dev (B,3,3) double holds the INVERSE of each forward matrix, inverted in double by the caller (the
+ * division of work of imx_warp_affine_u8).  src_dev (B,H,W) uint8 with batch stride src_stride_b bytes -> dst_dev (B,H,W) uint8.
+ * Per destination pixel, in double without contraction: w = m6 x + m7 y + m8, s = w ? 32 / w : 0, X = sat_int(rint((m0 x + m1 y + m2) s)),
+ * likewise Y; tap X >> 5 with the fraction X & 31; four taps (0 outside the image) with 15-bit integer weights, rounded. */
+IMX_API int imx_warp_perspective_u8(imx_handle_t h, const uint8_t* src_dev, int64_t src_stride_b, const double* minv_dev,
+                                    uint8_t* dst_dev, int B, int H, int W, void* stream);
+/* GlueSparse.py:64-82 for B pairs: kpts0 projected by m_dev (B,3,3) double as cv2.perspectiveTransform does on float32 points (rounded
+ * to float32; proj_dev (B,N0,2) receives them unless NULL), cdist's distances in double, numpy's argmin in both directions (the lowest
+ * index wins among equal distances); (i, j) is a match when each is the other's nearest and the distance is < radius (the reference: 3).
+ * n{0,1}_dev: B int32 counts or NULL = all; rows past a count are never read and may hold NaN.
+ *   gt0_dev (B,N0) / gt1_dev (B,N1) int64: the partner's index or -1;
+ *   all_matches_dev (B,2,N0+N1) int64: the reference's columns -- the n matches ascending in j as (i, j), every unmatched i ascending
+ *       as (i, n1), every unmatched j ascending as (n0, j), with that pair's counts n0, n1; -1 past n_all = n0 + n1 - n;
+ *   n_matches_dev, n_all_dev (B) int32; a pair with a zero count has both 0 (the reference's skip sample, :52-61). */
+IMX_API int imx_gt_matches(imx_handle_t h, int B, const float* kpts0_dev, const int32_t* n0_dev, int N0,
+                           const float* kpts1_dev, const int32_t* n1_dev, int N1, const double* m_dev, double radius,
+                           float* proj_dev, int64_t* gt0_dev, int64_t* gt1_dev, int64_t* all_matches_dev,
+                           int32_t* n_matches_dev, int32_t* n_all_dev, void* stream);
+/* The objective of superglue_train.py:289-299 for the pairs of the LAST imx_superglue_forward / imx_match_pairs on this handle, whose
+ * score matrix, potentials and bin_score it reads from the workspace: loss_dev[b] = mean over the n_all[b] columns (x, y) of
+ * all_matches_dev (B,2,L), L = N0 + N1 of that forward, of -log(exp(Z[x][y])) in fp32, Z = S + u + v - norm; x = n0 / y = n1 is the
+ * dustbin.  A term whose exp underflows is +inf; n_all = 0 gives 0; the summation order is fixed.  With matches0_dev and gt0_dev
+ * (B,N0) int64 both given, stats_dev (B,3) int32 = [gt0 >= 0, matches0 > -1, matches0 == gt0 >= 0] counts.  Fails when no SuperGlue
+ * forward has run on the handle, when B or L are not that forward's, or when its workspaces were grown, released or overwritten since. */
+IMX_API int imx_match_loss(imx_handle_t h, int B, const int64_t* all_matches_dev, const int32_t* n_all_dev, int L,
+                           const int64_t* matches0_dev, const int64_t* gt0_dev, float* loss_dev, int32_t* stats_dev, void* stream);
+
 /* Parity-test taps: when enabled, forwards keep copies of named intermediates
  * ("x4","semi","desc","score_map","nms","kenc","gnn<i>","mdesc","scores_in","u","v", ...).
  * imx_debug_fetch copies one to HOST (synchronises the device); shape_out gets up to 4 dims. */
