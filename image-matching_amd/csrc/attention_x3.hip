@@ -18,11 +18,10 @@
 //   * 24 bf16 MFMAs of 32 cycles per 32 x 32 tile at HD = 32 instead of 32 fp32 MFMAs of 64 cycles; the VALU work (softmax,
 //     the splits) issues beneath the other waves' MFMAs instead of stopping the pipe (the fp32 MFMA shares the VALU datapath).
 #include "imx_kernels.h"
-#include "split3.h"
+#include "planes.h"
 
 namespace imx {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
@@ -36,61 +35,6 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 namespace {
-
-// ---- operand formats.  A format says how an fp32 operand is cut into 16-bit planes and which plane products are kept.
-// FmtX3: x = h + m + l in bf16 (8 significant bits each), six of the nine term products -- fp32 products to ~2^-24, any exponent.
-struct FmtX3 {
-  static constexpr int NP = 3, NT = 6;
-  static constexpr bool SCALED = false;
-  typedef __bf16 T;
-  typedef __bf16 x8 __attribute__((ext_vector_type(8)));
-  typedef __bf16 x4 __attribute__((ext_vector_type(4)));
-  typedef __bf16 x2 __attribute__((ext_vector_type(2)));
-  // term products, smallest first: planes (A, B) = (m,m) (h,l) (l,h) (h,m) (m,h) (h,h)
-  static __device__ __forceinline__ constexpr int pa(int i) { constexpr int t[6] = {1, 0, 2, 0, 1, 0}; return t[i]; }
-  static __device__ __forceinline__ constexpr int pb(int i) { constexpr int t[6] = {1, 2, 0, 1, 0, 0}; return t[i]; }
-  static __device__ __forceinline__ void split(float x0, float x1, x2 (&pl)[3]) { split3_pair(x0, x1, pl[0], pl[1], pl[2]); }
-  static __device__ __forceinline__ f32x16 mfma(x8 a, x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
-// FmtH2 (round 4): x s = h + m in fp16 (11 significant bits each: 22 bits, truncation 2^-22 |x|), THREE term products (h,m) (m,h)
-// (h,h) -- half the MFMAs of FmtX3 and a split of 2 instead of 3.5 VALU instructions per value (v_cvt_pk_f16_f32 rounds and packs
-// two values, the residual x - h is one v_dot2c_f32_f16 per value, exact).  fp16 has five exponent bits, so every operand is
-// scaled by a power of two s that brings the largest |value| of its (side, pair) (AttnArgs::amax: q, k, v maxima over the valid rows,
-// written by qkv_amax below or by the producing gnn_tail_x3) to [2^13, 2^14): every value within 2^-17 of the maximum keeps its 22 bits, smaller ones are exact to 2^-39 of
-// the maximum; P (<= 1) is scaled by 2^15 inside its exponential.  The powers of two cancel exactly (one fma in the softmax, the
-// final 1 / l).  Against a float64 evaluation the result is as close as the six-product bf16 form's on P.V (P's own rounding in
-// fp32 dominates both) and 0.66 x the fp32-MFMA kernel's error on Q.K^T (tools/f16_split_emul.py; tools/ubench/attn_x3_bench.cpp
-// measures all three kernels).
-struct FmtH2 {
-  static constexpr int NP = 2, NT = 3;
-  static constexpr bool SCALED = true;
-  typedef _Float16 T;
-  typedef _Float16 x8 __attribute__((ext_vector_type(8)));
-  typedef _Float16 x4 __attribute__((ext_vector_type(4)));
-  typedef _Float16 x2 __attribute__((ext_vector_type(2)));
-  static __device__ __forceinline__ constexpr int pa(int i) { constexpr int t[3] = {0, 1, 0}; return t[i]; }
-  static __device__ __forceinline__ constexpr int pb(int i) { constexpr int t[3] = {1, 0, 0}; return t[i]; }
-  static __device__ __forceinline__ void split(float x0, float x1, x2 (&pl)[2]) {
-    // constants through SGPRs behind an asm, as in split3.h (hipcc 7.2 folds a packed {-1, 0} into the inline constant -1.0)
-    unsigned lo_u, hi_u;
-    asm("s_mov_b32 %0, 0x0000bc00" : "=s"(lo_u));
-    asm("s_mov_b32 %0, 0xbc000000" : "=s"(hi_u));
-    const x2 lo = __builtin_bit_cast(x2, lo_u), hi = __builtin_bit_cast(x2, hi_u);
-    pl[0][0] = (_Float16)x0; pl[0][1] = (_Float16)x1;                                  // v_cvt_pk_f16_f32 (round to nearest even)
-    const float r0 = __builtin_amdgcn_fdot2(pl[0], lo, x0, false);                     // x0 - h0, exact
-    const float r1 = __builtin_amdgcn_fdot2(pl[0], hi, x1, false);
-    pl[1][0] = (_Float16)r0; pl[1][1] = (_Float16)r1;
-  }
-  static __device__ __forceinline__ f32x16 mfma(x8 a, x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
-// the power of two that brings a tensor whose largest |value| is `amax` (bit pattern) to [2^13, 2^14); exponents clamped so that the
-// scale, the product of two scales and their reciprocals stay normal fp32 numbers (amax in [2^-37, 2^73]: outside, fp32 attention
-// itself is degenerate)
-__device__ __forceinline__ float pow2_scale(unsigned amax_bits) {
-  unsigned e = (amax_bits >> 23) & 0xffu;
-  e = e < 90u ? 90u : e > 200u ? 200u : e;
-  return __builtin_bit_cast(float, (267u - e) << 23);
-}
 
 // FmtH2's softmax reference point.  The online softmax is exact for ANY per-row reference r >= max - 15.9 used consistently (P' =
 // 2^(s - r), the running sum and output rescaled by 2^(r_old - r_new); the common factor cancels in O / l): r = max - 15 puts the

@@ -15,7 +15,7 @@
 //     barrier | transform 1 | barrier | MFMAs 1, output transform, pool, stores -- five barriers where the fp32 form has ten.
 // The transform / split / MFMA phases are conv3x3_wino24h.hip's; the conv1a GEMM, the epilogue and the tile walk conv1ab_wino24.hip's.
 #include "imx_kernels.h"
-#include "wino24_pk.h"
+#include "wino24_h2.h"
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
@@ -29,36 +29,6 @@ typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 
 namespace {
-constexpr int OH = 8, OW = 16;                 // output pixels per workgroup (4 x 4 wtiles of 2 x 4)
-constexpr int RH = OH + 2, RW = OW + 2;        // conv1a patch (pad-1 halo)
-constexpr int IMG_H = RH + 2, IMG_W = RW + 2;  // image patch 12 x 20
-constexpr int RSH = 34;                        // conv1a half patch: pixel stride (32 channels + 2: wtile columns 4 px apart land 8 banks apart)
-constexpr int RAWSZ = 192 * RSH;               // 180 pixels + 12 pad (the conv1a GEMM's twelfth pixel block stores unmasked)
-constexpr int NPOS = 24;
-constexpr int VPLANE = NPOS * 4 * 16 * 8;      // halves per plane
-constexpr int UPOS = 2 * 4 * 64 * 8;           // halves of U per (chunk, position): [plane][wave][lane][8]
-constexpr int RING = 6;
-
-template <bool V>
-struct BoolC { static constexpr bool value = V; };
-
-__device__ __forceinline__ void split_h2(f32x2 x, f16x2& h, f16x2& m) {      // conv3x3_wino24h.hip
-  unsigned lo_u, hi_u;
-  asm("s_mov_b32 %0, 0x0000bc00" : "=s"(lo_u));
-  asm("s_mov_b32 %0, 0xbc000000" : "=s"(hi_u));
-  const f16x2 lo = __builtin_bit_cast(f16x2, lo_u), hi = __builtin_bit_cast(f16x2, hi_u);
-  h[0] = (_Float16)x[0]; h[1] = (_Float16)x[1];
-  const float r0 = __builtin_amdgcn_fdot2(h, lo, x[0], false);
-  const float r1 = __builtin_amdgcn_fdot2(h, hi, x[1], false);
-  m[0] = (_Float16)r0; m[1] = (_Float16)r1;
-}
-// the power of two that brings 32 x `bound` (>= 20 max|d| >= |V|) to 2^13
-__device__ __forceinline__ float v_scale_of_bound(float bound) {
-  unsigned e = (__builtin_bit_cast(unsigned, bound) >> 23) & 0xffu;
-  e = e < 60u ? 60u : e > 200u ? 200u : e;
-  return __builtin_bit_cast(float, (261u - e) << 23);
-}
-
 __global__ __launch_bounds__(256, 2) void conv1ab_wino24h(ConvArgs p, int tiles_x, int tiles_y, int ntiles) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_1h[];
   _Float16* Vp = reinterpret_cast<_Float16*>(smem_1h);                          // [2][VPLANE]
@@ -185,9 +155,10 @@ __global__ __launch_bounds__(256, 2) void conv1ab_wino24h(ConvArgs p, int tiles_
       w24_batch_b(o, hb, T);
 #pragma unroll
       for (int jj = 0; jj < 6; ++jj) {
-        f16x2 h, m;
-        split_h2(T[jj], h, m);
+        f16x2 hm[2];
+        FmtH2::split(T[jj][0], T[jj][1], hm);
         _Float16* d = vwr + ((jj * 4 * 4 + q) * 16) * 8;
+        const f16x2 h = hm[0], m = hm[1];
         *reinterpret_cast<f16x2*>(d) = h;
         *reinterpret_cast<f16x2*>(d + VPLANE) = m;
       }

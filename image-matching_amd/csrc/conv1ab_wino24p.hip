@@ -14,7 +14,7 @@
 // Every output sees conv1ab_wino24h's arithmetic in the same order: the two kernels agree bit for bit (tests/test_gpu_superpoint.py).
 // LDS: V 96 KB + conv1a half patches 2 x 26 KB + image patches + maxima table = 151 KB.
 #include "imx_kernels.h"
-#include "wino24_pk.h"
+#include "wino24_h2.h"
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -29,44 +29,7 @@ typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 
 namespace {
-constexpr int OH = 8, OW = 16;                 // output pixels per tile (4 x 4 wtiles of 2 x 4)
-constexpr int RH = OH + 2, RW = OW + 2;        // conv1a patch (pad-1 halo)
-constexpr int IMG_H = RH + 2, IMG_W = RW + 2;  // image patch 12 x 20
 constexpr int IMG_N = IMG_H * IMG_W;           // 240
-constexpr int RSH = 34;                        // conv1a half patch: pixel stride (32 channels + 2), conv1ab_wino24h.hip
-constexpr int RAWSZ = 192 * RSH;               // floats per tile: 180 pixels + 12 pad
-constexpr int NPOS = 24, NLP = 12, NG = 2;
-constexpr int VPLANE = NPOS * 4 * 16 * 8;      // halves per plane of a tile
-constexpr int VGRP = 2 * VPLANE;               // halves per tile
-constexpr int UPOS = 2 * 4 * 64 * 8;           // halves of U per (chunk, position): [plane][channel block][lane][8]
-constexpr int RING = 6;
-constexpr int XCH = 6 * 64 * 16;               // bytes of one wave's exchange block: the row stage's six results for the partner's tile (conv3x3_wino24p.hip)
-constexpr int AMAX_SLOTS = 256;
-
-template <bool V>
-struct BoolC { static constexpr bool value = V; };
-
-__device__ __forceinline__ void split_h2(f32x2 x, f16x2& h, f16x2& m) {      // conv3x3_wino24h.hip
-  unsigned lo_u, hi_u;
-  asm("s_mov_b32 %0, 0x0000bc00" : "=s"(lo_u));
-  asm("s_mov_b32 %0, 0xbc000000" : "=s"(hi_u));
-  const f16x2 lo = __builtin_bit_cast(f16x2, lo_u), hi = __builtin_bit_cast(f16x2, hi_u);
-  h[0] = (_Float16)x[0]; h[1] = (_Float16)x[1];
-  const float r0 = __builtin_amdgcn_fdot2(h, lo, x[0], false);
-  const float r1 = __builtin_amdgcn_fdot2(h, hi, x[1], false);
-  m[0] = (_Float16)r0; m[1] = (_Float16)r1;
-}
-__device__ __forceinline__ int lane_now() {                                    // conv3x3_wino24p.hip
-  int l;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-  return l;
-}
-// the power of two that brings 32 x `bound` (>= 20 max|d| >= |V|) to 2^13 (conv1ab_wino24h.hip)
-__device__ __forceinline__ float v_scale_of_bound(float bound) {
-  unsigned e = (__builtin_bit_cast(unsigned, bound) >> 23) & 0xffu;
-  e = e < 60u ? 60u : e > 200u ? 200u : e;
-  return __builtin_bit_cast(float, (261u - e) << 23);
-}
 
 __global__ __launch_bounds__(512) void conv1ab_wino24p(ConvArgs p, int tiles_x, int tiles_y, int ntiles) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_1p[];
@@ -224,9 +187,9 @@ __global__ __launch_bounds__(512) void conv1ab_wino24p(ConvArgs p, int tiles_x, 
       w24_batch_b(o, hb, T);
 #pragma unroll
       for (int jj = 0; jj < 6; ++jj) {
-        f16x2 h, m;
-        split_h2(T[jj], h, m);
-        v_store2(jj * 4 + i, h, m);
+        f16x2 hm[2];
+        FmtH2::split(T[jj][0], T[jj][1], hm);
+        v_store2(jj * 4 + i, hm[0], hm[1]);
       }
     };
     row_load(r1, 1);

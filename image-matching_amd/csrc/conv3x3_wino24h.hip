@@ -27,7 +27,7 @@
 //   barrier
 // LDS: V 48 KB + raw 30 KB + 1 KB = 79 KB per workgroup, two per CU.
 #include "imx_kernels.h"
-#include "wino24_pk.h"
+#include "wino24_h2.h"
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
@@ -41,17 +41,6 @@ typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
-constexpr int OH = 8, OW = 16;                 // output pixels per item (4 x 4 wtiles of 2 x 4)
-constexpr int RH = OH + 2, RW = OW + 2;        // input patch (pad-1 halo)
-constexpr int RSC = 10;                        // raw sub-patch: pixel stride (8 channels + 2), as in conv3x3_wino24.hip
-constexpr int RAWC = 192 * RSC;                // 180 pixels + pad, floats per 8-channel sub-patch
-constexpr int NSUB = 4;                        // 8-channel sub-patches per chunk
-constexpr int CKH = 32, NT = 64, NPOS = 24;
-constexpr int VPLANE = NPOS * 4 * 16 * 8;      // halves per plane (24576 bytes)
-constexpr int UPOS = 2 * 4 * 64 * 8;           // halves of U per (item block, chunk, position): [plane][wave][lane][8]
-constexpr int AMAX_SLOTS = 256;                // image b -> slot b % 256 (ConvArgs::amax_in / amax_out hold upper bounds, so sharing a slot is safe)
-constexpr int RING = 6;                        // positions of U in flight
-constexpr unsigned OOB = 0x7ffffff0u;          // byte offset beyond any image: buffer loads return 0
 #ifndef H_EXP
 #define H_EXP 0                                // timing experiments (tools/ubench/conv_h_bench.cpp): 1 no U refills, 2 no transform, 3 no patch loads / stores
 #endif
@@ -64,29 +53,6 @@ __device__ long long h_trace_buf[16 * 8];
 #else
 #define H_STAMP(i_)
 #endif
-template <bool V>
-struct BoolC { static constexpr bool value = V; };
-
-// x = h + m in fp16, two values at a time (attention_x3.hip's FmtH2::split; constants through SGPRs: hipcc 7.2 folds a packed
-// {-1, 0} into the inline constant -1.0)
-__device__ __forceinline__ void split_h2(f32x2 x, f16x2& h, f16x2& m) {
-  unsigned lo_u, hi_u;
-  asm("s_mov_b32 %0, 0x0000bc00" : "=s"(lo_u));
-  asm("s_mov_b32 %0, 0xbc000000" : "=s"(hi_u));
-  const f16x2 lo = __builtin_bit_cast(f16x2, lo_u), hi = __builtin_bit_cast(f16x2, hi_u);
-  h[0] = (_Float16)x[0]; h[1] = (_Float16)x[1];
-  const float r0 = __builtin_amdgcn_fdot2(h, lo, x[0], false);
-  const float r1 = __builtin_amdgcn_fdot2(h, hi, x[1], false);
-  m[0] = (_Float16)r0; m[1] = (_Float16)r1;
-}
-
-// s_v of an image: 32 x its largest |input| (>= the bound 20 max|d| of the transformed patch) goes to 2^13
-__device__ __forceinline__ float v_scale(unsigned amax_bits) {
-  unsigned e = (amax_bits >> 23) & 0xffu;
-  e = e < 60u ? 60u : e > 200u ? 200u : e;
-  return __builtin_bit_cast(float, (262u - e) << 23);
-}
-
 template <bool POOL, bool RELU>
 __global__ __launch_bounds__(256, 2) void conv3x3_wino24h(ConvArgs p, int tiles_x, int tiles_y, int nitems) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_h[];
@@ -240,9 +206,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino24h(ConvArgs p, int tiles_
       w24_batch_b(o, hb, T);
 #pragma unroll
       for (int jj = 0; jj < 6; ++jj) {
-        f16x2 h, m;
-        split_h2(T[jj], h, m);
+        f16x2 hm[2];
+        FmtH2::split(T[jj][0], T[jj][1], hm);
         _Float16* d = vwr + ((jj * 4 * 4 + q) * 16) * 8;          // position jj*4 + wave (the wave part sits in vwr), group q
+        const f16x2 h = hm[0], m = hm[1];
         *reinterpret_cast<f16x2*>(d) = h;
         *reinterpret_cast<f16x2*>(d + VPLANE) = m;
       }

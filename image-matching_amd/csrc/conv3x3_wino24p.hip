@@ -29,7 +29,7 @@
 //
 // LDS: V 2 tiles x 48 KB + raw patches 2 x 30 KB + 1 KB of maxima = 157 KB, one workgroup per CU.
 #include "imx_kernels.h"
-#include "wino24_pk.h"
+#include "wino24_h2.h"
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -44,21 +44,6 @@ typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
-constexpr int OH = 8, OW = 16;                 // output pixels per tile (4 x 4 wtiles of 2 x 4)
-constexpr int RH = OH + 2, RW = OW + 2;        // input patch (pad-1 halo)
-constexpr int RSC = 10;                        // raw sub-patch: pixel stride (8 channels + 2), as in conv3x3_wino24.hip
-constexpr int RAWC = 192 * RSC;                // 180 pixels + pad, floats per 8-channel sub-patch
-constexpr int NSUB = 4;                        // 8-channel sub-patches per chunk
-constexpr int NG = 2;                          // tiles per workgroup
-constexpr int CKH = 32, NT = 64, NPOS = 24;
-constexpr int NLP = 12;                        // positions per wave: transformed COLUMNS 3 ph .. 3 ph + 2, all four rows = positions 12 ph + lp, lp = jj*4 + i
-constexpr int VPLANE = NPOS * 4 * 16 * 8;      // halves per plane of a tile (24576 bytes)
-constexpr int VGRP = 2 * VPLANE;               // halves per tile
-constexpr int UPOS = 2 * 4 * 64 * 8;           // halves of U per (item block, chunk, position): [plane][channel block][lane][8]
-constexpr int AMAX_SLOTS = 256;                // image b -> slot b % 256 (conv3x3_wino24h.hip)
-constexpr int RING = 6;                        // of the wave's twelve positions, in flight (NLP % RING == 0)
-constexpr int XCH = 6 * 64 * 16;               // bytes of one wave's exchange block: the row stage's six results for the partner's tile
-constexpr unsigned OOB = 0x7ffffff0u;          // byte offset beyond any image: buffer loads return 0
 #ifdef P_TRACE
 // phase clocks (tools/ubench/conv_h_bench.cpp, -DP_TRACE): cycles of wave 0 of every 16th workgroup in each phase of chunk_step
 __device__ long long p_trace_buf[16 * 16];
@@ -68,37 +53,7 @@ __device__ long long p_trace_buf[16 * 16];
 #endif
 
 struct Tile { int b, y0, x0, live; };
-template <bool V>
-struct BoolC { static constexpr bool value = V; };
-
-// x = h + m in fp16, two values at a time (conv3x3_wino24h.hip).  (The residual and its conversion as one mixed-precision fma each --
-// v_fma_mixlo_f16 / v_fma_mixhi_f16, three instructions instead of four, the same bits -- measured the same: 1917 vs 1916 us on conv2a.)
-__device__ __forceinline__ void split_h2(f32x2 x, f16x2& h, f16x2& m) {
-  unsigned lo_u, hi_u;
-  asm("s_mov_b32 %0, 0x0000bc00" : "=s"(lo_u));
-  asm("s_mov_b32 %0, 0xbc000000" : "=s"(hi_u));
-  const f16x2 lo = __builtin_bit_cast(f16x2, lo_u), hi = __builtin_bit_cast(f16x2, hi_u);
-  h[0] = (_Float16)x[0]; h[1] = (_Float16)x[1];
-  const float r0 = __builtin_amdgcn_fdot2(h, lo, x[0], false);
-  const float r1 = __builtin_amdgcn_fdot2(h, hi, x[1], false);
-  m[0] = (_Float16)r0; m[1] = (_Float16)r1;
-}
-
-// the lane index, recomputed where it is called (a volatile asm is not hoisted out of the main loop: values derived from a kept
-// lane index are spilled to scratch there, and a scratch reload is a vector-memory operation that waits for the loads in flight)
-__device__ __forceinline__ int lane_now() {
-  int l;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-  return l;
-}
-
-// s_v of an image: 32 x its largest |input| (>= the bound 20 max|d| of the transformed patch) goes to 2^13 (conv3x3_wino24h.hip),
-// and its reciprocal (a power of two either way: equal to conv3x3_wino24h's division)
-__device__ __forceinline__ float v_scale(unsigned amax_bits) {
-  unsigned e = (amax_bits >> 23) & 0xffu;
-  e = e < 60u ? 60u : e > 200u ? 200u : e;
-  return __builtin_bit_cast(float, (262u - e) << 23);
-}
+// the reciprocal of v_scale (wino24_h2.h): a power of two either way, equal to conv3x3_wino24h's division
 __device__ __forceinline__ float v_scale_inv(unsigned amax_bits) {
   unsigned e = (amax_bits >> 23) & 0xffu;
   e = e < 60u ? 60u : e > 200u ? 200u : e;
@@ -377,9 +332,9 @@ __global__ __launch_bounds__(512) void conv3x3_wino24p(ConvArgs p, int tiles_x, 
       w24_batch_b(o, hb, T);
 #pragma unroll
       for (int jj = 0; jj < 6; ++jj) {
-        f16x2 h, m;
-        split_h2(T[jj], h, m);
-        v_store2(jj * 4 + i, h, m);
+        f16x2 hm[2];
+        FmtH2::split(T[jj][0], T[jj][1], hm);
+        v_store2(jj * 4 + i, hm[0], hm[1]);
       }
     };
     row_load(r1, 1);

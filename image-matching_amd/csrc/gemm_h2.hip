@@ -12,16 +12,17 @@
 //     to one (side, pair) (padded counts are multiples of 128: gemm_h2_supported).  A value keeps 22 bits down to 2^-16 of that
 //     maximum and is exact to 2^-38 of it below; rows past the pair's keypoint count are not covered by the maximum and are ZEROED
 //     while they are staged (their outputs are the bias: finite, as every form leaves them unused).
-// Work split, pipeline and epilogue are gemm_x3's: persistent workgroups walk 128 x BN tiles, the 32-k chunks of all their tiles one
-// stream; A rows arrive as fp32 float4, are scaled and split in registers (v_cvt_pk_f16_f32, two v_dot2c_f32_f16 residuals,
-// v_cvt_pk_f16_f32) and stored as two planes (80-byte rows) under the previous chunk's MFMAs.
+// The work split is gemm_x3's: persistent workgroups walk 128 x BN tiles, the 32-k chunks of all their tiles one stream; A rows arrive
+// as fp32 float4, are scaled and split in registers (planes.h: FmtH2) and stored as two planes (80-byte rows) under the previous chunk's MFMAs.
+// The pipeline is this kernel's own since round 6 (`frags` ahead of the MFMAs, the sched_barrier, both chunk bodies always executed, the
+// drained epilogue, the staggered start): the two stay two kernels, sharing the format (planes.h) and nothing of the schedule.
 #include "imx_kernels.h"
+#include "planes.h"
 #include <cstdint>
 #include <cstdlib>
 
 namespace imx {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
@@ -32,26 +33,6 @@ template <bool V>
 struct BoolC { static constexpr bool value = V; };
 
 constexpr int BM = 128, KC = 32, RS = 40;   // rows per tile, k per chunk, LDS row stride in halves (80 bytes: an odd number of 16-byte slots)
-
-// the power of two that brings `bound` (> 0) to [2^13, 2^14) (exponents clamped so that the scale and its reciprocal stay normal)
-__device__ __forceinline__ float pow2_of_bound(float bound) {
-  unsigned e = (__builtin_bit_cast(unsigned, bound) >> 23) & 0xffu;
-  e = e < 90u ? 90u : e > 200u ? 200u : e;
-  return __builtin_bit_cast(float, (267u - e) << 23);
-}
-
-// x = h + m in fp16, two values at a time (attention_x3.hip's FmtH2::split: constants through SGPRs behind an asm, hipcc 7.2 folds a
-// packed {-1, 0} into the inline constant -1.0, which v_dot2c_f32_f16 does not read as a packed pair)
-__device__ __forceinline__ void split_h2(float x0, float x1, f16x2& h, f16x2& m) {
-  unsigned lo_u, hi_u;
-  asm("s_mov_b32 %0, 0x0000bc00" : "=s"(lo_u));
-  asm("s_mov_b32 %0, 0xbc000000" : "=s"(hi_u));
-  const f16x2 lo = __builtin_bit_cast(f16x2, lo_u), hi = __builtin_bit_cast(f16x2, hi_u);
-  h[0] = (_Float16)x0; h[1] = (_Float16)x1;
-  const float r0 = __builtin_amdgcn_fdot2(h, lo, x0, false);
-  const float r1 = __builtin_amdgcn_fdot2(h, hi, x1, false);
-  m[0] = (_Float16)r0; m[1] = (_Float16)r1;
-}
 
 // position in a workgroup's stream of chunks: tile t (= row tile * column tiles + column tile), chunk c of its K; the tile's
 // (side, pair) index, its valid rows (local index < left) and the power of two of its A operand
@@ -98,7 +79,7 @@ __global__ __launch_bounds__(256, 2) void gemm_h2(GemmArgs p, const _Float16* __
       const int ksp = p.sa1_cross ? (1 - side) * p.aB + b : cu.sp;
       bound = fmaxf(bound, __builtin_bit_cast(float, ((cu32p)(uintptr_t)p.sa1)[(size_t)ksp * p.sa1_stride + p.sa1_off]));
     }
-    cu.sA = pow2_of_bound(fmaxf(bound, 1e-30f));
+    cu.sA = pow2_scale(fmaxf(bound, 1e-30f));
   };
   auto advance = [&](Cursor& cu) {          // block-uniform; past the end the cursor stays on the last chunk (harmless re-fetch)
     if (cu.c + 1 < nch) { ++cu.c; }
@@ -130,9 +111,9 @@ __global__ __launch_bounds__(256, 2) void gemm_h2(GemmArgs p, const _Float16* __
       f16x4 h, m;
 #pragma unroll
       for (int t = 0; t < 4; t += 2) {
-        f16x2 h2, m2;
-        split_h2(v[t], v[t + 1], h2, m2);
-        h[t] = h2[0]; h[t + 1] = h2[1]; m[t] = m2[0]; m[t + 1] = m2[1];
+        f16x2 pl[2];
+        FmtH2::split(v[t], v[t + 1], pl);
+        h[t] = pl[0][0]; h[t + 1] = pl[0][1]; m[t] = pl[1][0]; m[t + 1] = pl[1][1];
       }
       const int o = ((tid >> 3) + 32 * it) * RS + (tid & 7) * 4;
       *reinterpret_cast<f16x4*>(&Ad[0][o]) = h;
@@ -182,11 +163,10 @@ __global__ __launch_bounds__(256, 2) void gemm_h2(GemmArgs p, const _Float16* __
   };
   // three plane products per block, smallest first; the row blocks interleave so consecutive MFMAs use different accumulators
   auto step = [&](const f16x8 (&af)[RB][2], const f16x8 (&wf)[2]) __attribute__((always_inline)) {
-    constexpr int PA[3] = {0, 1, 0}, PB[3] = {1, 0, 0};
 #pragma unroll
-    for (int t = 0; t < 3; ++t)
+    for (int t = 0; t < FmtH2::NT; ++t)
 #pragma unroll
-      for (int rb = 0; rb < RB; ++rb) acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[rb][PA[t]], wf[PB[t]], acc[rb], 0, 0, 0);
+      for (int rb = 0; rb < RB; ++rb) acc[rb] = FmtH2::mfma(af[rb][FmtH2::pa(t)], wf[FmtH2::pb(t)], acc[rb]);
   };
 
   // Developer instrumentation (-DGH2_TRACE; tools/gemm_h2_trace.py, profiles/r06_gemm_h2_trace.txt): s_memtime of the first 64 workgroups at

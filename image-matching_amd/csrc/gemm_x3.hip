@@ -22,12 +22,11 @@
 //   B operand for one step and plane is one coalesced 1 KB load straight into registers (no LDS, no barrier), requested a chunk
 //   ahead; every workgroup of a column reads the same fragments (L2 / L1 resident: 3 x K x Npad x 2 bytes per layer).
 #include "imx_kernels.h"
-#include "split3.h"
+#include "planes.h"
 #include <cstdlib>
 
 namespace imx {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
@@ -80,9 +79,9 @@ __global__ __launch_bounds__(256, 2) void gemm_x3(GemmArgs p, const __bf16* __re
       bf16x4 h, m, l;
 #pragma unroll
       for (int t = 0; t < 4; t += 2) {
-        split_bf16x2 h2, m2, l2;
-        split3_pair(areg[it][t], areg[it][t + 1], h2, m2, l2);
-        h[t] = h2[0]; h[t + 1] = h2[1]; m[t] = m2[0]; m[t + 1] = m2[1]; l[t] = l2[0]; l[t + 1] = l2[1];
+        FmtX3::x2 pl[3];
+        FmtX3::split(areg[it][t], areg[it][t + 1], pl);
+        h[t] = pl[0][0]; h[t + 1] = pl[0][1]; m[t] = pl[1][0]; m[t + 1] = pl[1][1]; l[t] = pl[2][0]; l[t + 1] = pl[2][1];
       }
       const int o = ((tid >> 3) + 32 * it) * RS + (tid & 7) * 4;
       *reinterpret_cast<bf16x4*>(&Ad[0][o]) = h;
@@ -113,11 +112,10 @@ __global__ __launch_bounds__(256, 2) void gemm_x3(GemmArgs p, const __bf16* __re
 #pragma unroll
       for (int rb = 0; rb < RB; ++rb)
         af[rb][pl] = *reinterpret_cast<const bf16x8*>(&Ar[pl][(wr * WROWS + rb * 32 + i) * RS + s * 16 + kb * 8]);
-    constexpr int PA[6] = {1, 0, 2, 0, 1, 0}, PB[6] = {1, 2, 0, 1, 0, 0};
 #pragma unroll
-    for (int t = 0; t < 6; ++t)
+    for (int t = 0; t < FmtX3::NT; ++t)
 #pragma unroll
-      for (int rb = 0; rb < RB; ++rb) acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[rb][PA[t]], wf[PB[t]], acc[rb], 0, 0, 0);
+      for (int rb = 0; rb < RB; ++rb) acc[rb] = FmtX3::mfma(af[rb][FmtX3::pa(t)], wf[FmtX3::pb(t)], acc[rb]);
   };
 
   // epilogue from registers: lane (col = i, kb) holds rows (r & 3) + 8 (r >> 2) + 4 kb of its column; 32 lanes store 128

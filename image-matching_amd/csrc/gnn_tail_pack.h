@@ -1,4 +1,4 @@
-// gnn_tail_pack.h -- host side of gnn_tail_x3.hip: the weights of one GNN layer tail (mlp.0' -> ReLU -> mlp.3 + residual -> the next
+// gnn_tail_pack.h -- host side of gnn_tail.hip: the weights of one GNN layer tail (mlp.0' -> ReLU -> mlp.3 + residual -> the next
 // layer's q|k|v, or final_proj) as ONE stream of LDS images, in the order the kernel consumes them (the kernel reads it as images of
 // two k-steps = 24 KB, or of four = 48 KB with 8-wave workgroups: the stream is step-major, so both views are the same bytes).
 //
@@ -68,12 +68,12 @@ inline std::vector<uint16_t> gnn_tail_pack(const float* w1, int ld1, const float
   return out;
 }
 
-// gnn_tail_h2.hip: the same stream with every weight as TWO fp16 planes of w s, s = the power of two that brings its matrix's largest
+// gnn_tail.hip as FmtH2: the same stream with every weight as TWO fp16 planes of w s, s = the power of two that brings its matrix's largest
 // |value| to [2^13, 2^14); images of [step][block][plane (2)][lane][8 halves] (8 KB per k-step).  Also returns what the kernel's
 // bounds need: the reciprocals of the three scales and the largest column L1 norm of w1 / w2 (a column = one output channel).
 // loose_h / loose_x: estimates of how far gnn_tail_h2's BOUNDS of the hidden activations h and of x' sit above typical values --
 // (largest column L1 norm) / (median column L2 norm) of mlp.0' (times the same ratio of mlp.3 for x'), times an activation crest
-// factor of 2^4.  The bound is brought to 2^13 (pow2_of_bound); a value keeps both fp16 planes down to 2^-3, so beyond 2^16 the
+// factor of 2^4.  The bound is brought to 2^13 (planes.h: pow2_scale); a value keeps both fp16 planes down to 2^-3, so beyond 2^16 the
 // typical operand starts to lose its low plane and sg_forward (imx_superglue.cpp; the guard: imx_host.h: tail_h2_safe) runs that layer's tail on three bf16 planes instead.
 // w_spread (round 6): over the three matrices, (largest |w|) / (median over output columns of their largest |w|): each matrix carries ONE power of
 // two, so a runaway column pushes the typical one towards fp16's low end (2^12: the typical weight still keeps the scheme's 22 bits)

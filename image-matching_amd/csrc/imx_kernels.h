@@ -266,7 +266,7 @@ struct AttnArgs {
 hipError_t launch_attention(const AttnArgs& a, hipStream_t s);
 hipError_t launch_qkv_amax(const AttnArgs& a, unsigned* amax, hipStream_t s);
 bool attention_takes_x3(const AttnArgs& a);      // launch_attention would run attention_x3.hip's kernels for these arguments
-// The tail of one GNN layer of the throughput path in one launch (gnn_tail_x3.hip): hidden = relu([x | att] W1' + b1); x += hidden W2 + b2;
+// The tail of one GNN layer of the throughput path in one launch (gnn_tail.hip): hidden = relu([x | att] W1' + b1); x += hidden W2 + b2;
 // out = x W3 + b3 (the next layer's q|k|v, n3 = 3 d, or final_proj, n3 = d) -- six bf16 term products per fp32 product; d = 128.
 // `stream` = gnn_tail_pack() of the three weight matrices (gnn_tail_pack.h).
 struct GnnTailArgs {
@@ -282,7 +282,7 @@ struct GnnTailArgs {
   unsigned* amax;
   const int* n0; const int* n1;
   int B, N0p, N1p, N0, N1;
-  // gnn_tail_h2.hip (three fp16 plane products of two-plane operands): the weights as gnn_tail_pack_h2() wrote them, the reciprocals of the
+  // gnn_tail.hip as FmtH2 (three fp16 plane products of two-plane operands): the weights as gnn_tail_pack_h2() wrote them, the reciprocals of the
   // powers of two they were scaled by, the largest column L1 norms / |bias| of mlp.0' and mlp.3 (bounds of the hidden activations and
   // of x'), the (side, pair) maxima of this layer's x (amax_x_in, [2 B] bit patterns) and of its attention's v (amax_v: the [2 B][4]
   // table AttnArgs::amax of the same layer), whether that attention was a cross layer, and where the maxima of x' go (amax_x_out,

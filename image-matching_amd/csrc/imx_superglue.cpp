@@ -142,7 +142,7 @@ int sg_forward(imx_handle_t h, int B, const SgSide sd[2], int64_t* m0, int64_t* 
   // "attention" = f16x2: the two-plane fp16 form of the throughput attention scales q, k, v by powers of two taken from their maxima
   // over the valid rows of every (side, pair) -- [2 B][4] words per layer, zeroed once per forward; written by the fused layer tail that produces the layer's
   // q|k|v (gnn_tail_x3's epilogue), else by qkv_amax (layer 0, whose q|k|v is a plain GEMM; the unfused A/B forms)
-  // (the same buffer carries, behind the q / k / v tables, one word per (layer, side, pair) for max |x|: gnn_tail_h2.hip's bounds)
+  // (the same buffer carries, behind the q / k / v tables, one word per (layer, side, pair) for max |x|: gnn_tail.hip's FmtH2 bounds)
   unsigned* amax = nullptr;
   unsigned* amax_x = nullptr;
   if (h->opt.attention != 0 && !h->opt.mfma_f32) {
@@ -206,7 +206,7 @@ int sg_forward(imx_handle_t h, int B, const SgSide sd[2], int64_t* m0, int64_t* 
     const bool last = l + 1 == h->layers.size();
     const GemmW& nx = last ? h->final_proj : h->layers[l + 1].qkv;
     GnnSmallArgs ga{x, att, L.mlp1.wf, L.mlp1.b, L.mlp2.wf, L.mlp2.b, nx.wf, nx.b, last ? mdesc : qkv, R, d, nx.N};
-    // Throughput form: the same three products in one launch on the bf16 pipe (gnn_tail_x3.hip): "gnn_tail" = auto takes it whenever the
+    // Throughput form: the same three products in one launch on the bf16 pipe (gnn_tail.hip, FmtX3): "gnn_tail" = auto takes it whenever the
     // latency forms do not apply (M > 4096 rows; measured against three gemm_x3 launches: 40 vs 50 us at 8224 rows, 65 vs 86 at 32768,
     // 256 vs 300 at 131072) -- so results do not depend on the batch size under "latency_forms" = off.
     GnnTailArgs ta{x, att, L.tail_stream, L.mlp1.b, L.mlp2.b, nx.b, last ? mdesc : qkv, R, d, nx.N};
@@ -216,7 +216,7 @@ int sg_forward(imx_handle_t h, int B, const SgSide sd[2], int64_t* m0, int64_t* 
     }
     const bool tail_ok = !small_form && !h->opt.mfma_f32 && L.tail_stream && nx.Npad == nx.N && gnn_tail_x3_supported(ta);
     const bool tail = tail_ok && h->opt.gnn_tail != 0;
-    // "gnn_tail" = auto / fused: the same launch as three fp16 plane products (gnn_tail_h2.hip) where the two-plane attention runs (its
+    // "gnn_tail" = auto / fused: the same launch as three fp16 plane products (gnn_tail.hip, FmtH2) where the two-plane attention runs (its
     // v maxima bound att) -- the maxima of x come from the previous layer's tail, for layer 0 from rows_amax
     bool tail_h2 = false;
     // ("auto": only where the bounds that scale the operands are tight enough for both fp16 planes -- L.h2c.loose_*, computed from the

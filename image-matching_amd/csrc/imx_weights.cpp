@@ -396,7 +396,7 @@ int finalize_superglue(imx_handle_t h) {
   int npf = 0;
   build_gemm_host(raw, "final_proj", "", d, d, nullptr, wfin, bfin, npf);
   if (upload_gemm(h, h->final_proj, wfin, bfin, d, d, npf, "final_proj")) return -1;
-  // the fused layer tail of the throughput path (gnn_tail_x3.hip): one weight stream per layer, in consumption order
+  // the fused layer tail of the throughput path (gnn_tail.hip): one weight stream per layer, in consumption order
   if (d == 128) {
     for (int l = 0; l < c.num_gnn_layers; ++l) {
       const bool last = l + 1 == c.num_gnn_layers;

@@ -1,6 +1,6 @@
 // gemm_x3_bench.cpp -- times imx::launch_gemm_x3 (and the fp32-MFMA gemm_ws it replaces) on the GNN's three products at 64 pairs.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -x hip tools/ubench/gemm_x3_bench.cpp image-matching_amd/csrc/gemm_x3.hip \
-//         -o tools/ubench/gemm_x3_bench      (-DIMX_SPLIT_DOT2=0 for the shift/subtract split: A/B of csrc/split3.h)
+//         -o tools/ubench/gemm_x3_bench
 #include "../../image-matching_amd/csrc/imx_kernels.h"
 #include <hip/hip_runtime.h>
 #include <cstdint>

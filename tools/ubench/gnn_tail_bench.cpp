@@ -1,7 +1,7 @@
 // gnn_tail_bench.cpp -- times imx::launch_gnn_tail_x3 (the fused GNN layer tail) against the three gemm_x3 launches it replaces, at the
 // C3 step's row count (64 pairs: 131072 rows, d = 128), and checks both against a float64 evaluation of a few rows.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -amdgpu-mfma-vgpr-form=1 -Iinclude -x hip tools/ubench/gnn_tail_bench.cpp \
-//         image-matching_amd/csrc/gnn_tail_x3.hip image-matching_amd/csrc/gnn_tail_h2.hip image-matching_amd/csrc/gemm_x3.hip -o tools/ubench/gnn_tail_bench
+//         image-matching_amd/csrc/gnn_tail.hip image-matching_amd/csrc/gemm_x3.hip -o tools/ubench/gnn_tail_bench
 #include "../../image-matching_amd/csrc/imx_kernels.h"
 #include "../../image-matching_amd/csrc/gnn_tail_pack.h"
 #include <hip/hip_runtime.h>
@@ -11,9 +11,6 @@
 #include <cstring>
 #include <vector>
 using namespace imx;
-#ifdef GT_TRACE
-namespace imx { void gnn_tail_trace_dump(); }
-#endif
 namespace imx { thread_local const char* last_form = nullptr; }
 static std::vector<uint16_t> x3_planes(const std::vector<float>& w, int K, int N) {      // gemm_x3's B-fragment order (imx_weights.cpp: split_bf16x3)
   const int nst = K / 16;
@@ -141,9 +138,6 @@ int main(int argc, char** argv) {
     for (int i = 0; i < 20; ++i) run();
     hipEventRecord(e1, 0); hipEventSynchronize(e1);
     float ms; hipEventElapsedTime(&ms, e0, e1);
-#ifdef GT_TRACE
-    if (form == 0) gnn_tail_trace_dump();
-#endif
     if (form == 3) {             // the maxima of x' and of q | k | v against the host's (every row valid here)
       int bad = 0;
       for (int sp = 0; sp < 2 * PB; ++sp) {

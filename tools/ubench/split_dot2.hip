@@ -1,4 +1,4 @@
-// split_dot2.hip -- is the v_dot2c_f32_bf16 form of the three-term bf16 split (csrc/split3.h) the same bits as the shift / subtract
+// split_dot2.hip -- is the v_dot2c_f32_bf16 form of the three-term bf16 split (csrc/planes.h: split3_pair) the same bits as the shift / subtract
 // form?  Every fp32 value whose low 8 mantissa bits are swept over 2^24 patterns x a set of exponents (incl. zeros, subnormals, the
 // largest finite values, both signs); the three planes must agree bit for bit, and h + m + l == x exactly where x is normal and
 // the residuals are not subnormal.
@@ -8,8 +8,7 @@
 #include <cstdint>
 #include <cstring>
 #include <vector>
-#define IMX_SPLIT_DOT2 1
-#include "../../image-matching_amd/csrc/split3.h"
+#include "../../image-matching_amd/csrc/planes.h"
 using namespace imx;
 __device__ __forceinline__ void split_ref(float x0, float x1, split_bf16x2& h, split_bf16x2& m, split_bf16x2& l) {
   h[0] = (__bf16)x0; h[1] = (__bf16)x1;
