@@ -339,13 +339,8 @@ hipError_t launch_conv1ab_wino24(const ConvArgs& a, hipStream_t s) {
   if (!a.first || !a.pool || a.Cin != 64 || a.Cout != 64 || !a.wu24) return hipErrorInvalidValue;
   const int tiles_x = (a.W + OW - 1) / OW, tiles_y = (a.H + OH - 1) / OH, ntiles = tiles_x * tiles_y * a.B;
   const size_t lds = (size_t)(2 * VSZ + RAWSZ + IMG_H * IMG_W) * sizeof(float);
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorUnknown;
-    ncu = prop.multiProcessorCount;
-  }
+  const int ncu = device_cu_count();
+  if (!ncu) return hipErrorUnknown;
   const dim3 grid((unsigned)(ntiles < 2 * ncu ? ntiles : 2 * ncu));     // persistent: two workgroups per CU
   last_form = "conv1ab_wino24:f32";
   static const bool trace = getenv("IMX_WINO_TRACE") != nullptr;     // developer instrumentation, read once per process

@@ -260,13 +260,8 @@ hipError_t launch_conv1ab_wino24h(const ConvArgs& a, hipStream_t s) {
   if (!conv1ab_wino24h_supported(a)) return hipErrorInvalidValue;
   const int tiles_x = (a.W + OW - 1) / OW, tiles_y = (a.H + OH - 1) / OH, ntiles = tiles_x * tiles_y * a.B;
   const size_t lds = (size_t)2 * VPLANE * 2 + (size_t)(RAWSZ + IMG_H * IMG_W + 4) * sizeof(float);
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorUnknown;
-    ncu = prop.multiProcessorCount;
-  }
+  const int ncu = device_cu_count();
+  if (!ncu) return hipErrorUnknown;
   static unsigned long long attr = 0;
   raise_lds_limit(reinterpret_cast<const void*>(conv1ab_wino24h), (int)lds, attr);
   const dim3 grid((unsigned)(ntiles < 2 * ncu ? ntiles : 2 * ncu));     // persistent: two workgroups per CU

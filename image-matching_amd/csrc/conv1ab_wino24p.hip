@@ -389,13 +389,8 @@ bool conv1ab_wino24p_supported(const ConvArgs& a) { return conv1ab_wino24h_suppo
 // workgroups, fills more of the chip)
 bool conv1ab_wino24p_preferred(const ConvArgs& a) {
   if (!conv1ab_wino24p_supported(a)) return false;
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return false;
-    ncu = prop.multiProcessorCount;
-  }
+  const int ncu = device_cu_count();
+  if (!ncu) return false;
   const long long tiles = (long long)((a.W + OW - 1) / OW) * ((a.H + OH - 1) / OH) * a.B;
   return (tiles + NG - 1) / NG >= 2LL * ncu;
 }
@@ -405,13 +400,8 @@ hipError_t launch_conv1ab_wino24p(const ConvArgs& a, hipStream_t s) {
   const int tiles_x = (a.W + OW - 1) / OW, tiles_y = (a.H + OH - 1) / OH, ntiles = tiles_x * tiles_y * a.B;
   const int npairs = (ntiles + NG - 1) / NG;
   const size_t lds = (size_t)NG * VGRP * 2 + (size_t)(NG * RAWSZ + NG * IMG_N + 8) * sizeof(float) + AMAX_SLOTS * sizeof(unsigned);
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorUnknown;
-    ncu = prop.multiProcessorCount;
-  }
+  const int ncu = device_cu_count();
+  if (!ncu) return hipErrorUnknown;
   static unsigned long long attr = 0;
   raise_lds_limit(reinterpret_cast<const void*>(conv1ab_wino24p), (int)lds, attr);
   const dim3 grid((unsigned)(npairs < ncu ? npairs : ncu));     // persistent: one workgroup per CU

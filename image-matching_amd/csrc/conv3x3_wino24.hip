@@ -381,13 +381,8 @@ hipError_t launch_t(const ConvArgs& a, hipStream_t s) {
   const int tiles_x = (a.W + OW - 1) / OW, tiles_y = (a.H + OH - 1) / OH;
   const int nitems = tiles_x * tiles_y * a.B * (a.Cout / NT);
   const size_t lds = (size_t)(2 * VSZ + 2 * RAWC) * sizeof(float);
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorUnknown;
-    ncu = prop.multiProcessorCount;
-  }
+  const int ncu = device_cu_count();
+  if (!ncu) return hipErrorUnknown;
   auto k = conv3x3_wino24<POOL, RELU, false>;
   auto kt = conv3x3_wino24<POOL, RELU, true>;
   static unsigned long long attr[2] = {0, 0};

@@ -361,13 +361,8 @@ hipError_t launch_h(const ConvArgs& a, hipStream_t s) {
   const int tiles_x = (a.W + OW - 1) / OW, tiles_y = (a.H + OH - 1) / OH;
   const int nitems = tiles_x * tiles_y * a.B * (a.Cout / NT);
   const size_t lds = (size_t)2 * VPLANE * 2 + (size_t)NSUB * RAWC * sizeof(float) + AMAX_SLOTS * sizeof(unsigned);
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorUnknown;
-    ncu = prop.multiProcessorCount;
-  }
+  const int ncu = device_cu_count();
+  if (!ncu) return hipErrorUnknown;
   auto k = conv3x3_wino24h<POOL, RELU>;
   static unsigned long long attr = 0;
   raise_lds_limit(reinterpret_cast<const void*>(k), (int)lds, attr);

@@ -583,13 +583,8 @@ hipError_t launch_p2(const ConvArgs& a, hipStream_t s) {
   const int ntiles = tiles_x * tiles_y * a.B;
   const int nitems = ((ntiles + NG - 1) / NG) * (a.Cout / NT);
   const size_t lds = (size_t)NG * VGRP * 2 + (size_t)NG * NSUB * RAWC * sizeof(float) + AMAX_SLOTS * sizeof(unsigned);
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorUnknown;
-    ncu = prop.multiProcessorCount;
-  }
+  const int ncu = device_cu_count();
+  if (!ncu) return hipErrorUnknown;
   auto k = conv3x3_wino24p<POOL, RELU, FASTW, INZ>;
   static unsigned long long attr = 0;
   raise_lds_limit(reinterpret_cast<const void*>(k), (int)lds, attr);
@@ -622,13 +617,8 @@ bool conv3x3_wino24p_supported(const ConvArgs& a) {
 // form, with twice the items and two workgroups per CU, fills more of the chip.
 bool conv3x3_wino24p_preferred(const ConvArgs& a) {
   if (!conv3x3_wino24p_supported(a)) return false;
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return false;
-    ncu = prop.multiProcessorCount;
-  }
+  const int ncu = device_cu_count();
+  if (!ncu) return false;
   const long long tiles = (long long)((a.W + OW - 1) / OW) * ((a.H + OH - 1) / OH) * a.B;
   return ((tiles + NG - 1) / NG) * (a.Cout / NT) >= ncu;
 }

@@ -346,13 +346,8 @@ hipError_t launch_gemm_h2(const GemmArgs& a, const void* wh2, hipStream_t s) {
   if (!gemm_h2_supported(a) || !wh2) return hipErrorInvalidValue;
   const _Float16* wx = static_cast<const _Float16*>(wh2);
   // persistent: two workgroups per CU; fewer tiles than that -> one workgroup per tile
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-  }
-  const int want = 2 * cus;
+  const int cus = device_cu_count();
+  const int want = 2 * (cus > 0 ? cus : 256);
   // (64-wide tiles where the 128-wide ones leave a workgroup a single tile -- mlp.3 at C5 -- measured: 1.34 vs 1.09 ms per step, kept wide)
   const bool wide = a.Npad % 128 == 0;
   const int nct = a.Npad / (wide ? 128 : 64), ntiles = ((a.M + BM - 1) / BM) * nct;

@@ -241,13 +241,8 @@ hipError_t launch_gemm_x3(const GemmArgs& a, const void* wx3, hipStream_t s) {
   const bool wide = a.Npad % 128 == 0;
   const int nct = a.Npad / (wide ? 128 : 64), ntiles = ((a.M + BM - 1) / BM) * nct;
   // persistent: two workgroups per CU; fewer tiles than that -> one workgroup per tile
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-  }
-  const int want = 2 * cus;
+  const int cus = device_cu_count();
+  const int want = 2 * (cus > 0 ? cus : 256);
   last_form = "gemm_x3:bf16x3";
   const dim3 grid((unsigned)(ntiles < want ? ntiles : want));
 #define IMX_X3(BN_)                                                                                      \

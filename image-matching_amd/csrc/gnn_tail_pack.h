@@ -74,7 +74,7 @@ inline std::vector<uint16_t> gnn_tail_pack(const float* w1, int ld1, const float
 // loose_h / loose_x: estimates of how far gnn_tail_h2's BOUNDS of the hidden activations h and of x' sit above typical values --
 // (largest column L1 norm) / (median column L2 norm) of mlp.0' (times the same ratio of mlp.3 for x'), times an activation crest
 // factor of 2^4.  The bound is brought to 2^13 (planes.h: pow2_scale); a value keeps both fp16 planes down to 2^-3, so beyond 2^16 the
-// typical operand starts to lose its low plane and sg_forward (imx_superglue.cpp; the guard: imx_host.h: tail_h2_safe) runs that layer's tail on three bf16 planes instead.
+// typical operand starts to lose its low plane and plan_superglue (imx_superglue.cpp; the guard: imx_host.h: tail_h2_safe) runs that layer's tail on three bf16 planes instead.
 // w_spread (round 6): over the three matrices, (largest |w|) / (median over output columns of their largest |w|): each matrix carries ONE power of
 // two, so a runaway column pushes the typical one towards fp16's low end (2^12: the typical weight still keeps the scheme's 22 bits)
 struct GnnTailH2Consts { float w1_inv, w2_inv, w3_inv, l1_1, l1_2, loose_h, loose_x, w_spread; };

@@ -263,7 +263,7 @@ constexpr float kLinearSpreadMax = 4096.f;       // the guard of gemm_h2's and g
                                                  // column's weights keep fewer than the scheme's 22 bits -- tests/test_gpu_heavy.py: a q / k channel at 2^14 used 0.8 of the tolerance)
 inline bool gemm_h2_weights_ok(const GemmW& W) { return W.wh2 && W.wh2_inv > 0.f && W.wh2_spread <= kLinearSpreadMax && W.K % 32 == 0 && W.Npad % 64 == 0; }
 
-// Each weights-derived guard is decided here, once: the launch sequences (sp_detect, sg_forward) and the "arith_guard" text of
+// Each weights-derived guard is decided here, once: the planners (plan_superpoint, plan_superglue) and the "arith_guard" text of
 // imx_get_option (imx_options.cpp) call the same functions.
 // conv chain: how far the typical output channel of the worst 3x3 layer (conv1a's plain weights included) sits below its layer's one scale
 inline float conv_chain_spread(const imx_handle_s* h) {
@@ -307,16 +307,20 @@ struct SgSide {
   const int32_t* n; int N, H, W;
 };
 int sg_forward(imx_handle_t h, int B, const SgSide sd[2], int64_t* m0, int64_t* m1, float* ms0, float* ms1, hipStream_t s);
-// What a linear layer of the GNN may ask of gemm() beside its operands.  `a` carries the OPTIONAL fields of GemmArgs only (its operand
-// fields are gemm()'s own arguments): the (side, pair) row structure, the q|k|v maxima the epilogue should write (amax: gemm_x3 /
-// gemm_h2), the scale sources of gemm_h2's A operand (sa0 / sa1) and the word its epilogue should leave for the next kernel (amax_row).
-// want_h2: the caller planned the whole chain on fp16 planes.  done / h2: what the launch actually did.
-struct GemmExtra {
-  GemmArgs a{};
-  bool want_h2 = false, done = false, h2 = false;
-};
-int gemm(imx_handle_t h, hipStream_t s, const char* name, const GemmW& W, const float* a0, int lda0, int K0, const float* a1,
-         int lda1, int K1, const float* res, int ldr, float* out, int ldo, int M, bool relu, GemmExtra* ex = nullptr);
+// A linear layer / 1x1 convolution: gemm() launches the form it is told.  gemm_args() fills the operand fields of GemmArgs over `opt`,
+// which carries the OPTIONAL ones (the GNN's linear layers: the (side, pair) row structure, the q|k|v maxima the epilogue should
+// write, gemm_h2's scale sources and the word its epilogue leaves).  gemm_form() is the small / x3 / tiled rule of a plain launch:
+// plan_superglue and the overload without a form (kenc, convPb, convDb) ask it; only the planner picks H2 or X3Amax.
+enum class GemmForm : unsigned char { Small, H2, X3, X3Amax, Tiled };
+inline GemmArgs gemm_args(const GemmW& W, const float* a0, int lda0, int K0, const float* a1, int lda1, int K1, const float* res, int ldr,
+                          float* out, int ldo, int M, bool relu, GemmArgs opt = GemmArgs{}) {
+  opt.a0 = a0; opt.lda0 = lda0; opt.K0 = K0; opt.a1 = a1; opt.lda1 = lda1; opt.K1 = K1; opt.w = W.w; opt.bias = W.b; opt.res = res; opt.ldr = ldr;
+  opt.out = out; opt.ldo = ldo; opt.M = M; opt.N = W.N; opt.Npad = W.Npad; opt.relu = relu ? 1 : 0;
+  return opt;
+}
+GemmForm gemm_form(const Options& o, const GemmW& W, const GemmArgs& g);
+int gemm(imx_handle_t h, hipStream_t s, const char* name, GemmForm form, const GemmW& W, GemmArgs g);
+inline int gemm(imx_handle_t h, hipStream_t s, const char* name, const GemmW& W, const GemmArgs& g) { return gemm(h, s, name, gemm_form(h->opt, W, g), W, g); }
 
 // imx_trainpairs.cpp
 // after sg_forward, by the entry point that called it: keeps the per-pair counts of that forward where imx_match_loss can read them later

@@ -61,6 +61,19 @@ inline void raise_lds_limit(const void* kern, int bytes, unsigned long long& don
   if (bit) __atomic_fetch_or(&done_mask, bit, __ATOMIC_RELEASE);
 }
 
+// The CU count of the CURRENT device, 0 if the query fails: what the persistent-grid launchers size their grids by and the
+// *_preferred predicates compare with.  Cached per device ordinal (devices past 63 ask every time), for the same reason as above.
+inline int device_cu_count() {
+  static int cached[64] = {};
+  int dev = 0, n = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 0;
+  const bool slot = dev >= 0 && dev < 64;
+  if (slot && (n = __atomic_load_n(&cached[dev], __ATOMIC_RELAXED)) > 0) return n;
+  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return 0;
+  if (slot) __atomic_store_n(&cached[dev], n, __ATOMIC_RELAXED);
+  return n;
+}
+
 // ---------------------------------------------------------------- conv3x3 (MFMA fp32, implicit GEMM)
 struct ConvArgs {
   const float* in;    // NHWC (B,H,W,Cin); FIRST mode: grayscale images (B,H,W), images >= split come from in2

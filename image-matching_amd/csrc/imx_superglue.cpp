@@ -1,59 +1,217 @@
-// imx_superglue.cpp -- the SuperGlue launch sequence of libimx.so (sg_forward), with the form planner of its fp16-plane chain, and
-// gemm(): the one place a linear layer / 1x1 convolution picks its kernel form (also SuperPoint's convPb / convDb).
+// imx_superglue.cpp -- the SuperGlue side of libimx.so: gemm_form() / gemm(), the forms of a linear layer / 1x1 convolution (also
+// SuperPoint's convPb / convDb); plan_superglue(), the ONE place a forward's kernel forms are chosen; and
+// sg_forward(), which allocates the workspaces, has the plan built and launches from it.
 #include "imx_host.h"
 
 #include <cmath>
 
 namespace imx::host {
 
-// `ex` (optional; the GNN's linear layers): see GemmExtra in imx_host.h.  ex->done says whether the q|k|v maxima ex->a.amax asks for
-// were written from the epilogue (else the caller runs launch_qkv_amax)
-int gemm(imx_handle_t h, hipStream_t s, const char* name, const GemmW& W, const float* a0, int lda0, int K0, const float* a1,
-         int lda1, int K1, const float* res, int ldr, float* out, int ldo, int M, bool relu, GemmExtra* ex) {
-  if (K0 + K1 != W.K) return fail(h, "internal: gemm '%s' K mismatch (%d+%d vs %d)", name, K0, K1, W.K);
-  auto with_operands = [&](GemmArgs t) {      // t: the optional fields (all zero for a plain launch)
-    t.a0 = a0; t.lda0 = lda0; t.K0 = K0; t.a1 = a1; t.lda1 = lda1; t.K1 = K1; t.w = W.w; t.bias = W.b; t.res = res; t.ldr = ldr;
-    t.out = out; t.ldo = ldo; t.M = M; t.N = W.N; t.Npad = W.Npad; t.relu = relu ? 1 : 0;
-    return t;
-  };
-  GemmArgs g = with_operands(GemmArgs{});
-  if (ex) { ex->done = false; ex->h2 = false; }
-  // Four forms, each with its reason:
-  //   gemm_small  M <= 4096 rows (one or two pairs): the latency form ("latency_forms": auto / off / on);
-  //   gemm_h2     the GNN's plain linear layers in the throughput path: three fp16 plane products, operands scaled by their actual
-  //               (side, pair) maxima ("linear" = auto / f16x2; the caller decides it for the whole chain: want_h2);
-  //   gemm_x3     the throughput form of everything else: fp32 products as six bf16 term products on the bf16 matrix pipe;
-  //   gemm_tiled  fp32 MFMA: the "mfma" = "f32" A/B reference of the parity tests and the fallback for shapes gemm_x3 rejects.
-  // Measured per layer inside the C3 step (64 pairs, gemm_x3 vs the fp32-MFMA forms of round 2): mlp.0 1.85 vs 2.57 ms, mlp.3
-  // 1.11 vs 1.45, convPb 0.23 vs 0.51, convDb 0.25 vs 0.35, q|k|v 2.06 vs 2.08.
-  const Options& o = h->opt;
-  const bool small = gemm_small_supported(g) && (o.latency_forms >= 0 ? o.latency_forms != 0 : M <= 4096);
-  const bool x3 = !small && !o.mfma_f32 && W.wx3 && gemm_x3_supported(g);
-  if (ex && ex->want_h2) {
-    GemmArgs gh = with_operands(ex->a);
-    gh.w_inv = W.wh2_inv;
-    if (small || o.mfma_f32 || !gemm_h2_weights_ok(W) || !gemm_h2_supported(gh))
-      return fail(h, "internal: gemm '%s' was planned on fp16 planes but cannot run there", name);
-    ex->done = ex->a.amax != nullptr;
-    ex->h2 = true;
-    if (h->debug) {        // developer instrumentation: chunk stamps of the first 64 workgroups (all zeros unless gemm_h2.hip was built with -DGH2_TRACE); the LAST launch's stay
-      WS(trc, unsigned long long, (std::string("sg.gh2_trace_") + name).c_str(), (size_t)64 * 128 * sizeof(unsigned long long));
-      HIP_OK(h, hipMemsetAsync(trc, 0, (size_t)64 * 128 * sizeof(unsigned long long), s));
-      gh.trace = trc;
-      tap(h, (std::string("gh2_trace_") + name).c_str(), trc, {64, 256});
-    }
-    RUN(name, launch_gemm_h2(gh, W.wh2, s));
-    return 0;
+// Four forms of a plain launch, each with its reason:
+//   gemm_small  M <= 4096 rows (one or two pairs): the latency form ("latency_forms": auto / off / on);
+//   gemm_x3     the throughput form: fp32 products as six bf16 term products on the bf16 matrix pipe;
+//   gemm_tiled  fp32 MFMA: the "mfma" = "f32" A/B reference of the parity tests and the fallback for shapes gemm_x3 rejects;
+//   gemm_h2     (the planner's choice only, for the GNN's whole chain: SgPlan::lin_h2) three fp16 plane products, operands scaled by
+//               their actual (side, pair) maxima ("linear" = auto / f16x2).
+// Measured per layer inside the C3 step (64 pairs, gemm_x3 vs the fp32-MFMA forms of round 2): mlp.0 1.85 vs 2.57 ms, mlp.3
+// 1.11 vs 1.45, convPb 0.23 vs 0.51, convDb 0.25 vs 0.35, q|k|v 2.06 vs 2.08.
+GemmForm gemm_form(const Options& o, const GemmW& W, const GemmArgs& g) {
+  if (gemm_small_supported(g) && (o.latency_forms >= 0 ? o.latency_forms != 0 : g.M <= 4096)) return GemmForm::Small;
+  return !o.mfma_f32 && W.wx3 && gemm_x3_supported(g) ? GemmForm::X3 : GemmForm::Tiled;
+}
+
+int gemm(imx_handle_t h, hipStream_t s, const char* name, GemmForm form, const GemmW& W, GemmArgs g) {
+  if (g.K0 + g.K1 != W.K) return fail(h, "internal: gemm '%s' K mismatch (%d+%d vs %d)", name, g.K0, g.K1, W.K);
+  if (form == GemmForm::H2 && h->debug) {        // developer instrumentation: chunk stamps of the first 64 workgroups (all zeros unless gemm_h2.hip was built with -DGH2_TRACE); the LAST launch's stay
+    WS(trc, unsigned long long, (std::string("sg.gh2_trace_") + name).c_str(), (size_t)64 * 128 * sizeof(unsigned long long));
+    HIP_OK(h, hipMemsetAsync(trc, 0, (size_t)64 * 128 * sizeof(unsigned long long), s));
+    g.trace = trc;
+    tap(h, (std::string("gh2_trace_") + name).c_str(), trc, {64, 256});
   }
-  if (ex && ex->a.amax && x3) {
-    const GemmArgs ga = with_operands(ex->a);
-    if (gemm_x3_amax_supported(ga)) { g = ga; ex->done = true; }
-  }
-  RUN(name, small ? launch_gemm_small(g, s) : x3 ? launch_gemm_x3(g, W.wx3, s) : launch_gemm(g, s));
+  RUN(name, form == GemmForm::Small ? launch_gemm_small(g, s) : form == GemmForm::H2 ? launch_gemm_h2(g, W.wh2, s) :
+            form == GemmForm::Tiled ? launch_gemm(g, s) : launch_gemm_x3(g, W.wx3, s));
   return 0;
 }
 
-// ----------------------------------------------------------------------------- SuperGlue
+// ----------------------------------------------------------------------------- SuperGlue: the plan
+namespace {
+
+// shapes and workspaces of one forward (allocated before the plan is built: the kernels' predicates see the real arguments)
+struct SgWork {
+  int B, N0, N1, N0p, N1p, R, d;
+  const int32_t *n0, *n1;
+  float *x, *att, *qkv, *hid, *mdesc;
+  // "attention" = f16x2: the two-plane fp16 form of the throughput attention scales q, k, v by powers of two taken from their maxima
+  // over the valid rows of every (side, pair) -- amax: [2 B][4] words per layer, zeroed once per forward; written by the epilogue of the
+  // kernel that produces the layer's q|k|v, else by qkv_amax.  amax_x, behind them: one word per (layer, side, pair) for max |x|, the
+  // scale of gemm_h2's / gnn_tail_h2's x operand.  Null: no tables ("attention" = bf16x3, "mfma" = f32)
+  unsigned *amax, *amax_x;
+};
+enum class TailForm : unsigned char { LayerSmall, TailH2, TailX3, Unfused };
+struct SgLayerPlan {
+  bool project;                  // q|k|v is projected here (else the previous layer's fused tail left it)
+  GemmForm qkv, mlp1, mlp2;      // the plain linear launches (qkv where `project`, mlp1 / mlp2 where the tail is unfused)
+  unsigned char rows_amax;       // rows_amax computes max |x| (nobody left it): 1 = before the projection, 2 = before the tail, 0 = not at all
+  bool qkv_amax;                 // the separate pass computes the q|k|v maxima (no epilogue wrote them)
+  bool f16x2;                    // the attention's format
+  TailForm tail;                 // (its epilogue leaves the NEXT layer's q|k|v maxima where f16x2, and max |x'|: tail_args)
+};
+struct SgPlan {
+  bool small_form;               // the latency forms (one or two pairs; "latency_forms")
+  bool epilogue_max;             // the tables exist and a projection's epilogue writes the q|k|v maxima ("qkv_amax" = kernel: never)
+  // "linear" = auto / f16x2: the plain linear layers of the GNN -- every layer's q|k|v, mlp.0' and mlp.3 where the tail is not fused
+  // (descriptor_dim 256: C5), layer 0's q|k|v and final_proj otherwise -- as gemm_h2.  Decided for the whole chain: the two-plane
+  // attention's tables exist and its kernel runs, the throughput forms apply, every matrix passes the spread guard.
+  bool lin_h2;
+  SgLayerPlan layers[IMX_MAX_GNN_LAYERS];      // (the layer count is bounded at imx_create: no heap per forward)
+  bool final_proj, rows_amax_final;     // final_proj is a launch of its own (the last tail is unfused), as final_form
+  GemmForm final_form;
+};
+
+enum Site { kQkv, kMlp1, kMlp2, kFinal };
+const char* const kSiteName[] = {"qkv_proj", "gnn_mlp1", "gnn_mlp2", "final_proj"};
+const GemmW& lin_w(imx_handle_t h, Site st, size_t l) {
+  return st == kFinal ? h->final_proj : st == kQkv ? h->layers[l].qkv : st == kMlp1 ? h->layers[l].mlp1 : h->layers[l].mlp2;
+}
+// the arguments of layer l's plain linear launch `st` as form f (kFinal: l = the number of layers)
+GemmArgs lin(imx_handle_t h, const SgWork& w, Site st, size_t l, GemmForm f, bool epilogue_max) {
+  const GemmW& W = lin_w(h, st, l);
+  const int d = w.d;
+  unsigned* const tab = w.amax ? w.amax + 8 * w.B * l : nullptr;                   // the layer's q|k|v maxima; [.][3]: max |hidden|
+  unsigned* const xmax = w.amax ? w.amax_x + (size_t)2 * w.B * l : nullptr;
+  GemmArgs o{};
+  if (f == GemmForm::H2 || f == GemmForm::X3Amax) {              // the (side, pair) row structure, and where a q|k|v epilogue leaves its maxima
+    o.an0 = w.n0; o.an1 = w.n1; o.aB = w.B; o.aN0p = w.N0p; o.aN1p = w.N1p; o.aN0 = w.N0; o.aN1 = w.N1;
+    o.sa0_stride = o.sa1_stride = o.amax_row_stride = 1;
+    if (st == kQkv && epilogue_max) o.amax = tab;
+  }
+  if (f == GemmForm::H2) {
+    o.w_inv = W.wh2_inv;
+    o.sa0 = xmax;
+    if (st == kMlp1) {                   // [x | att]: max |v| bounds att; the epilogue leaves max |hidden|
+      o.sa1 = tab; o.sa1_stride = 4; o.sa1_off = 2; o.sa1_cross = h->cfg.gnn_layer_is_cross[l] ? 1 : 0;
+      o.amax_row = tab; o.amax_row_stride = 4; o.amax_row_off = 3;
+    } else if (st == kMlp2) {            // hidden; the epilogue leaves max |x'|: the next projection's scale
+      o.sa0 = tab; o.sa0_stride = 4; o.sa0_off = 3;
+      o.amax_row = xmax + 2 * w.B;
+    }
+  }
+  switch (st) {
+    case kQkv: return gemm_args(W, w.x, d, d, nullptr, 0, 0, nullptr, 0, w.qkv, 3 * d, w.R, false, o);
+    case kMlp1: return gemm_args(W, w.x, d, d, w.att, d, d, nullptr, 0, w.hid, 2 * d, w.R, true, o);   // merge folded in
+    case kMlp2: return gemm_args(W, w.hid, 2 * d, 2 * d, nullptr, 0, 0, w.x, d, w.x, d, w.R, false, o);
+    default: return gemm_args(W, w.x, d, d, nullptr, 0, 0, nullptr, 0, w.mdesc, d, w.R, false, o);
+  }
+}
+AttnArgs attn_args(imx_handle_t h, const SgWork& w, size_t l, bool f16x2) {
+  AttnArgs a{};
+  a.qkv = w.qkv; a.out = w.att; a.B = w.B; a.N0p = w.N0p; a.N1p = w.N1p; a.d = w.d; a.heads = HEADS;
+  a.n0 = w.n0; a.n1 = w.n1; a.N0 = w.N0; a.N1 = w.N1; a.cross = h->cfg.gnn_layer_is_cross[l];
+  a.mfma_f32 = h->opt.mfma_f32; a.latency_forms = h->opt.latency_forms; a.qblocks = h->opt.attention_qblocks;
+  if (f16x2) a.amax = w.amax + 8 * w.B * l;
+  return a;
+}
+// The three products after the attention -- mlp.0', mlp.3 + residual and the NEXT layer's q|k|v (final_proj after the last layer) -- in
+// ONE launch.  Latency form: gnn_small.hip, the same arithmetic, bit for bit, as the three gemm_small launches it replaces.
+const GemmW& next_w(imx_handle_t h, size_t l) { return l + 1 == h->layers.size() ? h->final_proj : h->layers[l + 1].qkv; }
+GnnSmallArgs small_args(imx_handle_t h, const SgWork& w, size_t l) {
+  const GnnLayer& L = h->layers[l];
+  const GemmW& nx = next_w(h, l);
+  return GnnSmallArgs{w.x, w.att, L.mlp1.wf, L.mlp1.b, L.mlp2.wf, L.mlp2.b, nx.wf, nx.b, l + 1 == h->layers.size() ? w.mdesc : w.qkv, w.R, w.d, nx.N};
+}
+// Throughput form (gnn_tail.hip): on the bf16 pipe (FmtX3; "gnn_tail" = auto takes it whenever the latency forms do not apply, so
+// results do not depend on the batch size under "latency_forms" = off -- measured against three gemm_x3 launches: 40 vs 50 us at 8224
+// rows, 65 vs 86 at 32768, 256 vs 300 at 131072), or as three fp16 plane products (FmtH2) where the two-plane attention runs: its v
+// maxima bound att, the maxima of x come from the previous layer's tail, for layer 0 from rows_amax.
+GnnTailArgs tail_args(imx_handle_t h, const SgWork& w, size_t l, TailForm form, bool f16x2) {
+  const GnnLayer& L = h->layers[l];
+  const GemmW& nx = next_w(h, l);
+  const bool last = l + 1 == h->layers.size(), h2 = form == TailForm::TailH2;
+  GnnTailArgs t{w.x, w.att, L.tail_stream, L.mlp1.b, L.mlp2.b, nx.b, last ? w.mdesc : w.qkv, w.R, w.d, nx.N};
+  const bool max_out = f16x2 && !last;         // the next layer's attention takes the same form (same shapes): its maxima come out of this tail
+  if (max_out || h2) { t.n0 = w.n0; t.n1 = w.n1; t.B = w.B; t.N0p = w.N0p; t.N1p = w.N1p; t.N0 = w.N0; t.N1 = w.N1; }
+  if (max_out) t.amax = w.amax + 8 * w.B * (l + 1);
+  if (h2) {
+    t.stream_h2 = L.tail_stream_h2;
+    t.w1_inv = L.h2c.w1_inv; t.w2_inv = L.h2c.w2_inv; t.w3_inv = L.h2c.w3_inv;
+    t.l1_1 = L.h2c.l1_1; t.l1_2 = L.h2c.l1_2; t.bmax_1 = L.bmax_1; t.bmax_2 = L.bmax_2;
+    t.amax_x_in = w.amax_x + (size_t)2 * w.B * l; t.amax_v = w.amax + 8 * w.B * l;
+    t.amax_x_out = last ? nullptr : w.amax_x + (size_t)2 * w.B * (l + 1);      // (max |x'| for the next layer)
+    t.cross = h->cfg.gnn_layer_is_cross[l];
+  }
+  return t;
+}
+
+// Every form of the forward, from the handle (options, weights and their guards) and the shapes; a form whose kernel predicate
+// disagrees fails HERE, before anything is launched.  have_*: what the launches planned so far leave behind for the next one.
+int plan_superglue(imx_handle_t h, const SgWork& w, SgPlan& P) {
+  const Options& o = h->opt;
+  const size_t nl = h->layers.size();
+  if (nl > IMX_MAX_GNN_LAYERS) return fail(h, "internal: %zu GNN layers", nl);
+  const int d = w.d;
+  const bool takes_x3 = attention_takes_x3(attn_args(h, w, 0, false));      // (shapes and options only: the same for every layer)
+  P.small_form = o.latency_forms >= 0 ? o.latency_forms != 0 : w.R <= 4096;
+  // ("qkv_amax" = "kernel": the maxima of a projected q|k|v by the separate pass even where the projection's epilogue can write them --
+  // the A/B switch of tests/test_gpu_superglue.py; the two must agree bit for bit)
+  P.epilogue_max = w.amax && o.qkv_amax == 0;
+  P.lin_h2 = w.amax && !P.small_form && o.linear != 0 && w.N0p % 128 == 0 && w.N1p % 128 == 0 && linear_chain_h2_ok(h) && takes_x3;
+  auto linear = [&](Site st, size_t l, GemmForm& f) -> int {
+    const GemmW& W = lin_w(h, st, l);
+    if (P.lin_h2) {
+      f = GemmForm::H2;
+      return gemm_h2_weights_ok(W) && gemm_h2_supported(lin(h, w, st, l, f, P.epilogue_max)) ? 0 : fail(h, "internal: gemm '%s' was planned on fp16 planes but cannot run there", kSiteName[st]);
+    }
+    f = gemm_form(o, W, lin(h, w, st, l, GemmForm::Tiled, false));
+    if (f == GemmForm::X3 && st == kQkv && P.epilogue_max && gemm_x3_amax_supported(lin(h, w, st, l, GemmForm::X3Amax, true))) f = GemmForm::X3Amax;
+    return 0;
+  };
+  bool have_qkv = false, have_qkv_max = false, have_x_max = false;
+  for (size_t l = 0; l < nl; ++l) {
+    const GnnLayer& L = h->layers[l];
+    SgLayerPlan& p = P.layers[l] = SgLayerPlan{};
+    const bool last = l + 1 == nl;
+    const GemmW& nx = next_w(h, l);
+    p.project = !have_qkv;
+    if (p.project) {
+      if (linear(kQkv, l, p.qkv)) return -1;
+      if (P.lin_h2 && !have_x_max) p.rows_amax = 1;
+      have_x_max = have_x_max || P.lin_h2;
+      have_qkv_max = p.qkv == GemmForm::X3Amax || (p.qkv == GemmForm::H2 && P.epilogue_max);
+    }
+    p.f16x2 = w.amax && takes_x3 && (attn_f16x2_ok(L) || o.attention == 1);   // ("attention" = f16x2 forces it: the guard's A/B)
+    // (the maxima also scale gnn_mlp1's [x | att] on the fp16 planes where lin_h2 holds -- max |v| bounds att -- so they are written for
+    // every layer then, also where the guard runs this layer's attention on bf16x3)
+    p.qkv_amax = (p.f16x2 || P.lin_h2) && !have_qkv_max;
+    have_qkv = have_qkv_max = false;
+    p.tail = TailForm::Unfused;
+    if (P.small_form && o.latency_forms != 2 && L.mlp1.Npad == 2 * d && L.mlp2.Npad == d && nx.Npad == nx.N && gnn_layer_small_supported(small_args(h, w, l))) {
+      p.tail = TailForm::LayerSmall;
+    } else if (!P.small_form && !o.mfma_f32 && o.gnn_tail != 0 && L.tail_stream && nx.Npad == nx.N && gnn_tail_x3_supported(tail_args(h, w, l, TailForm::TailX3, p.f16x2))) {
+      // "gnn_tail" = auto: the fp16 form only where the bounds that scale the operands are tight enough for both planes (L.h2c.loose_*,
+      // computed from the weights at imx_finalize_weights); "fused" forces it, "bf16x3" the other
+      const bool h2 = p.f16x2 && o.gnn_tail != 2 && L.tail_stream_h2 && (tail_h2_safe(L) || o.gnn_tail == 1) && gnn_tail_h2_supported(tail_args(h, w, l, TailForm::TailH2, p.f16x2));
+      p.tail = h2 ? TailForm::TailH2 : TailForm::TailX3;
+    }
+    bool x_max_out = false;                    // the tail leaves max |x'| for the next layer
+    if (p.tail == TailForm::Unfused) {
+      if (linear(kMlp1, l, p.mlp1) || linear(kMlp2, l, p.mlp2)) return -1;
+      x_max_out = P.lin_h2;
+    } else {
+      have_qkv = !last;
+      have_qkv_max = p.tail != TailForm::LayerSmall && p.f16x2 && !last;
+      x_max_out = p.tail == TailForm::TailH2 && !last;
+    }
+    if ((p.tail == TailForm::TailH2 || (p.tail == TailForm::Unfused && P.lin_h2)) && !have_x_max) p.rows_amax = 2;
+    have_x_max = x_max_out;
+  }
+  P.final_proj = nl == 0 || P.layers[nl - 1].tail == TailForm::Unfused;
+  P.rows_amax_final = P.final_proj && P.lin_h2 && !have_x_max;
+  return P.final_proj ? linear(kFinal, nl, P.final_form) : 0;
+}
+
+}  // namespace
+
+// ----------------------------------------------------------------------------- SuperGlue: the launches
 int sg_forward(imx_handle_t h, int B, const SgSide sd[2], int64_t* m0, int64_t* m1, float* ms0, float* ms1, hipStream_t s) {
   if (!h->finalized[IMX_NET_SUPERGLUE]) return fail(h, "SuperGlue weights not finalized");
   const imx_config_t& c = h->cfg;
@@ -89,6 +247,18 @@ int sg_forward(imx_handle_t h, int B, const SgSide sd[2], int64_t* m0, int64_t* 
   WS(idx0, int, "sg.idx0", (size_t)B * N0p * 4);
   WS(idx1, int, "sg.idx1", (size_t)B * N1p * 4);
 
+  // every form of the forward, before anything is launched (the tables of maxima: SgWork)
+  SgWork w{B, N0, N1, N0p, N1p, R, d, sd[0].n, sd[1].n, x, att, qkv, hid, mdesc, nullptr, nullptr};
+  const size_t nl = h->layers.size(), amax_words = nl * 2 * B * 4 + (nl + 1) * 2 * B;
+  if (h->opt.attention != 0 && !h->opt.mfma_f32) {
+    WS(am, unsigned, "sg.amax", amax_words * 4);
+    w.amax = am;
+    w.amax_x = am + nl * 2 * B * 4;
+  }
+  unsigned* const amax = w.amax;
+  SgPlan P;
+  if (plan_superglue(h, w, P)) return -1;
+
   // descriptors -> rows; first keypoint-encoder layer (superglue_test.py:245-250): both sides, one launch
   // (with the per-pair counts: rows n[b] .. Np-1 of x and of the encoder's first layer are ZEROS whatever the caller's tensors hold
   // there.  Every later kernel is row-wise or masks by the counts, so a padding row stays finite for the whole forward -- which the
@@ -120,9 +290,9 @@ int sg_forward(imx_handle_t h, int B, const SgSide sd[2], int64_t* m0, int64_t* 
       const GemmW& g = h->kenc[i];
       const bool last = i + 1 == h->kenc.size();
       if (last) {
-        if (gemm(h, s, "kenc", g, cur, curw, g.K, nullptr, 0, 0, x, d, x, d, R, false)) return -1;   // desc + kenc(...)
+        if (gemm(h, s, "kenc", g, gemm_args(g, cur, curw, g.K, nullptr, 0, 0, x, d, x, d, R, false))) return -1;   // desc + kenc(...)
       } else {
-        if (gemm(h, s, "kenc", g, cur, curw, g.K, nullptr, 0, 0, nullptr, 0, nxt, g.N, R, true)) return -1;
+        if (gemm(h, s, "kenc", g, gemm_args(g, cur, curw, g.K, nullptr, 0, 0, nullptr, 0, nxt, g.N, R, true))) return -1;
         std::swap(cur, nxt);
         curw = g.N;
       }
@@ -134,128 +304,25 @@ int sg_forward(imx_handle_t h, int B, const SgSide sd[2], int64_t* m0, int64_t* 
     tap(h, "kenc", tk, {R, d});
   }
   // attentional GNN (superglue_test.py:122-138)
-  // Latency form (one or two pairs; "latency_forms"): the three products after the attention -- mlp.0', mlp.3 + residual and the
-  // NEXT layer's q|k|v (final_proj after the last layer) -- are ONE launch per layer (gnn_small.hip; same arithmetic, bit for bit,
-  // as the three gemm_small launches it replaces).
-  const bool small_form = h->opt.latency_forms >= 0 ? h->opt.latency_forms != 0 : R <= 4096;
-  bool have_next = false, have_mdesc = false, have_amax = false;
-  // "attention" = f16x2: the two-plane fp16 form of the throughput attention scales q, k, v by powers of two taken from their maxima
-  // over the valid rows of every (side, pair) -- [2 B][4] words per layer, zeroed once per forward; written by the fused layer tail that produces the layer's
-  // q|k|v (gnn_tail_x3's epilogue), else by qkv_amax (layer 0, whose q|k|v is a plain GEMM; the unfused A/B forms)
-  // (the same buffer carries, behind the q / k / v tables, one word per (layer, side, pair) for max |x|: gnn_tail.hip's FmtH2 bounds)
-  unsigned* amax = nullptr;
-  unsigned* amax_x = nullptr;
-  if (h->opt.attention != 0 && !h->opt.mfma_f32) {
-    const size_t nl = h->layers.size(), words = nl * 2 * B * 4 + (nl + 1) * 2 * B;
-    WS(am, unsigned, "sg.amax", words * 4);
-    HIP_OK(h, hipMemsetAsync(am, 0, words * 4, s));
-    amax = am;
-    amax_x = am + nl * 2 * B * 4;
-  }
-  long x_max_layer = -1;       // amax_x + 2 B x_max_layer holds max |x| of the CURRENT x (-1: not computed)
-  // ("qkv_amax" = "kernel": the maxima of a projected q|k|v by the separate pass even where the projection's epilogue can write them --
-  // the A/B switch of tests/test_gpu_superglue.py; the two must agree bit for bit)
-  const bool amax_by_kernel = h->opt.qkv_amax != 0;
-  // "linear" = auto / f16x2 (round 6): the plain linear layers of the GNN -- every layer's q|k|v, mlp.0' and mlp.3 where the tail is
-  // not fused (descriptor_dim 256: C5), layer 0's q|k|v and final_proj otherwise -- as three fp16 plane products (gemm_h2.hip), each
-  // operand scaled by its ACTUAL (side, pair) maximum: max |x| from rows_amax (layer 0) or the producing mlp.3's epilogue, max |v|
-  // (which bounds the attention output) from the q|k|v epilogue, max |hidden| from mlp.0's.  Decided for the whole chain: the
-  // two-plane attention's tables exist and its kernel runs, the throughput forms apply, every matrix passes the spread guard.
-  bool lin_h2 = amax && !small_form && h->opt.linear != 0 && N0p % 128 == 0 && N1p % 128 == 0 && R == B * (N0p + N1p) && linear_chain_h2_ok(h);
-  {
-    AttnArgs a{};
-    a.B = B; a.N0p = N0p; a.N1p = N1p; a.d = d; a.heads = HEADS; a.mfma_f32 = h->opt.mfma_f32; a.latency_forms = h->opt.latency_forms;
-    lin_h2 = lin_h2 && attention_takes_x3(a);
-  }
-  const size_t nl_ = h->layers.size();
-  auto extra = [&](unsigned* amax_out) {       // the (side, pair) row structure of this forward, and where a q|k|v epilogue should leave its maxima
-    GemmExtra e;
-    e.a.amax = amax_out; e.a.an0 = sd[0].n; e.a.an1 = sd[1].n; e.a.aB = B; e.a.aN0p = N0p; e.a.aN1p = N1p; e.a.aN0 = N0; e.a.aN1 = N1;
-    e.a.sa0_stride = e.a.sa1_stride = e.a.amax_row_stride = 1;
-    return e;
-  };
-  auto x_max_now = [&](size_t l) -> int {      // max |x| of the rows about to be projected, unless the kernel that produced x left it
-    if (x_max_layer != (long)l) RUN("rows_amax", launch_rows_amax_any(x, d, B, N0p, N1p, sd[0].n, sd[1].n, N0, N1, amax_x + (size_t)2 * B * l, s));
-    x_max_layer = (long)l;
+  if (amax) HIP_OK(h, hipMemsetAsync(amax, 0, amax_words * 4, s));
+  auto rows_amax = [&](size_t l) -> int {      // max |x| of the rows about to be projected
+    RUN("rows_amax", launch_rows_amax_any(x, d, B, N0p, N1p, sd[0].n, sd[1].n, N0, N1, w.amax_x + (size_t)2 * B * l, s));
     return 0;
   };
-  for (size_t l = 0; l < h->layers.size(); ++l) {
-    const GnnLayer& L = h->layers[l];
-    if (!have_next) {
-      // (the maxima of this q|k|v, if the two-plane attention will want them, out of the projection's epilogue where it can)
-      GemmExtra gam = extra(amax && !amax_by_kernel ? amax + 8 * B * l : nullptr);
-      if (lin_h2) {
-        if (x_max_now(l)) return -1;
-        gam.want_h2 = true; gam.a.sa0 = amax_x + (size_t)2 * B * l;
-      }
-      if (gemm(h, s, "qkv_proj", L.qkv, x, d, d, nullptr, 0, 0, nullptr, 0, qkv, 3 * d, R, false, &gam)) return -1;
-      have_amax = gam.done;
-    }
-    have_next = false;
-    AttnArgs a{};
-    a.qkv = qkv; a.out = att; a.B = B; a.N0p = N0p; a.N1p = N1p; a.d = d; a.heads = HEADS;
-    a.n0 = sd[0].n; a.n1 = sd[1].n; a.N0 = N0; a.N1 = N1; a.cross = c.gnn_layer_is_cross[l];
-    a.mfma_f32 = h->opt.mfma_f32; a.latency_forms = h->opt.latency_forms; a.qblocks = h->opt.attention_qblocks;
-    const bool f16x2 = amax && attention_takes_x3(a) && (attn_f16x2_ok(L) || h->opt.attention == 1);   // ("attention" = f16x2 forces it: the guard's A/B)
-    if (f16x2) a.amax = amax + 8 * B * l;
-    // (the maxima also scale gnn_mlp1's [x | att] on the fp16 planes where lin_h2 holds -- max |v| bounds att -- so they are written for
-    // every layer then, also where the guard runs this layer's attention on bf16x3)
-    if ((f16x2 || lin_h2) && !have_amax) RUN("qkv_amax", launch_qkv_amax(a, amax + 8 * B * l, s));
-    have_amax = false;
+  auto linear = [&](Site st, size_t l, GemmForm f) { return gemm(h, s, kSiteName[st], f, lin_w(h, st, l), lin(h, w, st, l, f, P.epilogue_max)); };
+  for (size_t l = 0; l < nl; ++l) {
+    const SgLayerPlan& p = P.layers[l];
+    if (p.rows_amax == 1 && rows_amax(l)) return -1;
+    if (p.project && linear(kQkv, l, p.qkv)) return -1;
+    const AttnArgs a = attn_args(h, w, l, p.f16x2);
+    if (p.qkv_amax) RUN("qkv_amax", launch_qkv_amax(a, amax + 8 * B * l, s));
     RUN("attention", launch_attention(a, s));
-    const bool last = l + 1 == h->layers.size();
-    const GemmW& nx = last ? h->final_proj : h->layers[l + 1].qkv;
-    GnnSmallArgs ga{x, att, L.mlp1.wf, L.mlp1.b, L.mlp2.wf, L.mlp2.b, nx.wf, nx.b, last ? mdesc : qkv, R, d, nx.N};
-    // Throughput form: the same three products in one launch on the bf16 pipe (gnn_tail.hip, FmtX3): "gnn_tail" = auto takes it whenever the
-    // latency forms do not apply (M > 4096 rows; measured against three gemm_x3 launches: 40 vs 50 us at 8224 rows, 65 vs 86 at 32768,
-    // 256 vs 300 at 131072) -- so results do not depend on the batch size under "latency_forms" = off.
-    GnnTailArgs ta{x, att, L.tail_stream, L.mlp1.b, L.mlp2.b, nx.b, last ? mdesc : qkv, R, d, nx.N};
-    if (f16x2 && !last) {              // the next layer's attention takes the same form (same shapes): its maxima come out of this tail
-      ta.amax = amax + 8 * B * (l + 1);
-      ta.n0 = sd[0].n; ta.n1 = sd[1].n; ta.B = B; ta.N0p = N0p; ta.N1p = N1p; ta.N0 = N0; ta.N1 = N1;
-    }
-    const bool tail_ok = !small_form && !h->opt.mfma_f32 && L.tail_stream && nx.Npad == nx.N && gnn_tail_x3_supported(ta);
-    const bool tail = tail_ok && h->opt.gnn_tail != 0;
-    // "gnn_tail" = auto / fused: the same launch as three fp16 plane products (gnn_tail.hip, FmtH2) where the two-plane attention runs (its
-    // v maxima bound att) -- the maxima of x come from the previous layer's tail, for layer 0 from rows_amax
-    bool tail_h2 = false;
-    // ("auto": only where the bounds that scale the operands are tight enough for both fp16 planes -- L.h2c.loose_*, computed from the
-    // weights at imx_finalize_weights; "fused" forces the fp16 form, "bf16x3" the other)
-    const bool h2_safe = tail_h2_safe(L);
-    if (tail && f16x2 && h->opt.gnn_tail != 2 && L.tail_stream_h2 && (h2_safe || h->opt.gnn_tail == 1)) {
-      ta.stream_h2 = L.tail_stream_h2;
-      ta.w1_inv = L.h2c.w1_inv; ta.w2_inv = L.h2c.w2_inv; ta.w3_inv = L.h2c.w3_inv;
-      ta.l1_1 = L.h2c.l1_1; ta.l1_2 = L.h2c.l1_2; ta.bmax_1 = L.bmax_1; ta.bmax_2 = L.bmax_2;
-      ta.amax_x_in = amax_x + (size_t)2 * B * l; ta.amax_v = amax + 8 * B * l; ta.amax_x_out = last ? nullptr : amax_x + (size_t)2 * B * (l + 1);
-      ta.cross = c.gnn_layer_is_cross[l];
-      ta.n0 = sd[0].n; ta.n1 = sd[1].n; ta.B = B; ta.N0p = N0p; ta.N1p = N1p; ta.N0 = N0; ta.N1 = N1;
-      tail_h2 = gnn_tail_h2_supported(ta);
-      if (tail_h2 && x_max_now(l)) return -1;
-    }
-    if (small_form && h->opt.latency_forms != 2 && L.mlp1.Npad == 2 * d && L.mlp2.Npad == d && nx.Npad == nx.N && gnn_layer_small_supported(ga)) {
-      RUN("gnn_layer", launch_gnn_layer_small(ga, s));
-      have_next = !last;
-      have_mdesc = last;
-      x_max_layer = -1;
-    } else if (tail) {
-      RUN("gnn_tail", tail_h2 ? launch_gnn_tail_h2(ta, s) : launch_gnn_tail_x3(ta, s));
-      have_next = !last;
-      have_mdesc = last;
-      have_amax = ta.amax != nullptr;
-      x_max_layer = tail_h2 && !last ? (long)l + 1 : -1;     // (the tail's epilogue leaves max |x'| for the next layer)
-    } else {
-      GemmExtra g1 = extra(nullptr), g2 = g1;
-      if (lin_h2) {                      // (x's maximum: this layer's q|k|v projection had it; v's: the attention's table)
-        if (x_max_now(l)) return -1;
-        g1.want_h2 = true; g1.a.sa0 = amax_x + (size_t)2 * B * l;
-        g1.a.sa1 = amax + 8 * B * l; g1.a.sa1_stride = 4; g1.a.sa1_off = 2; g1.a.sa1_cross = c.gnn_layer_is_cross[l] ? 1 : 0;
-        g1.a.amax_row = amax + 8 * B * l; g1.a.amax_row_stride = 4; g1.a.amax_row_off = 3;         // max |hidden|: the table's fourth word
-        g2.want_h2 = true; g2.a.sa0 = amax + 8 * B * l; g2.a.sa0_stride = 4; g2.a.sa0_off = 3;
-        g2.a.amax_row = amax_x + (size_t)2 * B * (l + 1);                                            // max |x'|: the next projection's scale
-      }
-      if (gemm(h, s, "gnn_mlp1", L.mlp1, x, d, d, att, d, d, nullptr, 0, hid, 2 * d, R, true, &g1)) return -1;   // merge folded in
-      if (gemm(h, s, "gnn_mlp2", L.mlp2, hid, 2 * d, 2 * d, nullptr, 0, 0, x, d, x, d, R, false, &g2)) return -1;
-      x_max_layer = lin_h2 ? (long)l + 1 : -1;
+    if (p.rows_amax == 2 && rows_amax(l)) return -1;
+    switch (p.tail) {
+      case TailForm::LayerSmall: RUN("gnn_layer", launch_gnn_layer_small(small_args(h, w, l), s)); break;
+      case TailForm::TailH2: RUN("gnn_tail", launch_gnn_tail_h2(tail_args(h, w, l, p.tail, p.f16x2), s)); break;
+      case TailForm::TailX3: RUN("gnn_tail", launch_gnn_tail_x3(tail_args(h, w, l, p.tail, p.f16x2), s)); break;
+      case TailForm::Unfused: if (linear(kMlp1, l, p.mlp1) || linear(kMlp2, l, p.mlp2)) return -1;
     }
     if (h->debug) {
       std::string nm = "gnn" + std::to_string(l);
@@ -264,14 +331,8 @@ int sg_forward(imx_handle_t h, int B, const SgSide sd[2], int64_t* m0, int64_t* 
       tap(h, nm.c_str(), tg, {R, d});
     }
   }
-  if (!have_mdesc) {
-    GemmExtra gf = extra(nullptr);
-    if (lin_h2) {
-      if (x_max_now(nl_)) return -1;
-      gf.want_h2 = true; gf.a.sa0 = amax_x + (size_t)2 * B * nl_;
-    }
-    if (gemm(h, s, "final_proj", h->final_proj, x, d, d, nullptr, 0, 0, nullptr, 0, mdesc, d, R, false, &gf)) return -1;
-  }
+  if (P.rows_amax_final && rows_amax(nl)) return -1;
+  if (P.final_proj && linear(kFinal, nl, P.final_form)) return -1;
   ScoreArgs sc{mdesc, mdesc + off1 * d, S, B, N0p, N1p, d, (float)(1.0 / std::sqrt((double)d))};
   RUN("score_gemm", launch_score_gemm(sc, s));
   float* part = nullptr;

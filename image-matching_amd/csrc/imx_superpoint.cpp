@@ -1,8 +1,131 @@
-// imx_superpoint.cpp -- the SuperPoint launch sequence of libimx.so: the shared encoder and both heads (sp_detect), keypoint selection,
-// and descriptor sampling (sp_describe).
+// imx_superpoint.cpp -- the SuperPoint side of libimx.so: plan_superpoint(), the ONE place the forms and activation layouts of the
+// eight 3x3 convolutions are chosen; sp_detect(), which launches the shared encoder and both heads from that
+// plan, then keypoint selection; and descriptor sampling (sp_describe).
 #include "imx_host.h"
 
 namespace imx::host {
+
+namespace {
+
+// The eight 3x3 launches: the input is (H >> level) x (W >> level); `swz` marks an output that may be written tile-swizzled (conv2a ->
+// conv2b, conv3a -> conv3b, conv4a -> conv4b: whole 8 x 16-pixel tiles, conv3x3_wino24p.hip).  Layer i reads act[i], writes act[i + 1].
+struct SpLayer { const char* name; int level; bool pool, first, last, swz; };
+constexpr int kSpN = 8;
+constexpr SpLayer kSpLayers[kSpN] = {{"conv1ab_pool", 0, true, true, false, false}, {"conv2a", 1, false, false, false, true},
+                                  {"conv2b_pool", 1, true, false, false, false}, {"conv3a", 2, false, false, false, true},
+                                  {"conv3b_pool", 2, true, false, false, false}, {"conv4a", 3, false, false, false, true},
+                                  {"conv4b", 3, false, false, false, false},     {"convPaDa", 3, false, false, true, false}};
+// The maxima of the fp16-plane chain live in 256 slots per layer (the kernels' LDS tables): a batch of more than 256 images runs its
+// 3x3 layers in slices of 256 images, each with its own tables, so that an image's scales -- and with them its low-order bits -- never
+// depend on which other images share the call (tests/test_gpu_superpoint.py: image b of a 260-image batch equals
+// the same image alone).
+constexpr int kSlice = 256;
+
+struct SpWork {                 // shapes and workspaces of one call
+  int B, H, W, split;
+  const float *img0, *img1;     // the images below `split`, the others
+  float* act[kSpN];             // each layer's output: a1, a2a, a2, a3a, a3, a4a, x4, heads
+  unsigned* amax;               // "sp.amax": one word per (slice, layer, image slot b % 256); null: the weights / options rule the chain out
+};
+enum class ConvForm : unsigned char { Direct, Wino, WinoH, WinoP, C1, C1H, C1P };
+constexpr hipError_t (*kConvLaunch[])(const ConvArgs&, hipStream_t) = {launch_conv3x3, launch_conv3x3_wino24, launch_conv3x3_wino24h, launch_conv3x3_wino24p,
+                                                                       launch_conv1ab_wino24, launch_conv1ab_wino24h, launch_conv1ab_wino24p};
+static_assert(sizeof(kConvLaunch) / sizeof(*kConvLaunch) == (size_t)ConvForm::C1P + 1, "one launcher per ConvForm, in the enum's order");
+struct SpStep { ConvForm form; unsigned char in_blocked, out_blocked; };      // (ConvArgs::in_blocked / out_blocked: 0 NHWC, 1 blocked, 2 swizzled)
+struct SpPlan {
+  // Activations between the Winograd layers are channel-blocked (B, C/8, H, W, 8) -- dense patch loads for the next layer
+  // (conv3x3_wino24.hip); the last 3x3 layer writes NHWC rows for the 1x1-conv GEMMs.  "conv" = direct (or a layer the Winograd
+  // kernels reject) keeps NHWC everywhere: the direct kernel reads nothing else.
+  bool blocked;
+  // "conv" = "wino": the Winograd products on the fp16 matrix pipe (conv3x3_wino24h.hip).  Each layer needs an upper bound of |input|
+  // per image, written by the PRODUCING layer's epilogue through atomicMax -- the fused first layer starts the chain; and weights whose
+  // transformed values fit ONE power-of-two scale per layer (conv_chain_h_ok).  One layer the fp16 kernel rejects, and the whole chain
+  // runs the fp32 kernels ("conv" reports it through imx_timing_form).
+  bool chain;
+  int nslice;
+  // det_only (imx_homography_adapt: only `semi` is consumed): 256 = convPa alone.  convPa | convDa share one launch whose Winograd
+  // weights are laid out by 64-channel output block, convPa's four first, so a Cout = 256 view of the same buffers IS convPa; the
+  // direct form's [9][Cin][Cout] weights have no such prefix: there the shared launch stays and only convDb is skipped.
+  int heads_cout;
+  // per layer, [0] for the full slices of 256 images, [1] for the last slice (the only one where the chain is off): the fill rules see
+  // the slice's image count and nothing else of it, so all full slices take the same forms
+  SpStep steps[2][kSpN];
+};
+
+// The arguments of layer li on slice sl but for the two layouts: those are the plan's to choose, and no rule below reads them
+ConvArgs conv_args(imx_handle_t h, const SpWork& w, const SpPlan& P, int li, int sl) {
+  const SpLayer& T = kSpLayers[li];
+  const ConvW& cw = h->conv[li];
+  const int hh = w.H >> T.level, ww = w.W >> T.level, cout = T.last ? P.heads_cout : cw.cout;
+  const int b0 = P.chain ? sl * kSlice : 0, nb = P.chain ? std::min(kSlice, w.B - b0) : w.B;
+  // (a slice's images are packed with their layout's own size; the SLICES of a tensor that may be swizzled are spaced by the padded
+  // size whatever each slice's layout is -- a short last slice can fall back to the blocked layout, and its region must not start
+  // inside the region of the slice before it)
+  const size_t ztile = (size_t)((hh + 7) / 8) * ((ww + 15) / 16) * 2048;       // floats per image and 16-channel block of a swizzled tensor
+  const size_t in_img = li && kSpLayers[li - 1].swz ? ztile * (cw.cin / 16) : (size_t)hh * ww * (T.first ? 1 : cw.cin);
+  const size_t out_img = T.swz ? ztile * (cout / 16) : (size_t)(T.pool ? hh / 2 : hh) * (T.pool ? ww / 2 : ww) * cout;
+  ConvArgs a{};
+  if (P.chain) {
+    unsigned* am = w.amax + (size_t)sl * kSpN * 256;
+    a.amax_out = T.last ? nullptr : am + (size_t)li * 256;
+    a.amax_in = li > 0 ? am + (size_t)(li - 1) * 256 : nullptr;
+    a.wuh = cw.wuh; a.u_scale_inv = cw.su_inv;
+    a.c1a_l1 = h->c1a_l1; a.c1a_bmax = h->c1a_bmax;
+  }
+  a.in = (li ? w.act[li - 1] : w.img0) + (size_t)b0 * in_img;
+  if (T.first) {                       // images below `split` come from img0, the others from img1: the slice's view of that
+    if (b0 >= w.split) { a.in = w.img1 + (size_t)(b0 - w.split) * in_img; a.split = nb; }
+    else { a.in2 = w.img1; a.split = w.split - b0; }
+  }
+  a.w = cw.w; a.wu24 = cw.wu24; a.bias = cw.b; a.w1 = h->w1; a.b1 = h->b1; a.out = w.act[li] + (size_t)b0 * out_img;
+  a.B = nb; a.H = hh; a.W = ww; a.Cin = cw.cin; a.Cout = cout; a.relu = 1; a.pool = T.pool; a.first = T.first;
+  return a;
+}
+
+// Each kernel predicate once, on conv_args(): the shape rules (*_supported) per layer, on the first slice's arguments -- they read the
+// layer's sizes, weights and pool flag (the pooled layers have Cin == Cout: their input-side size limit implies the unpooled output-side
+// one), not the image count; the fill rules (*_preferred) per layer on a full slice and on the last
+// one.  A tensor is swizzled where its producer AND its consumer run the pair kernel on the slice -- its stores are then 1 KB
+// contiguous per instruction ("conv_swizzle" = "off": never; bit-identical either way).
+void plan_superpoint(imx_handle_t h, const SpWork& w, bool det_only, SpPlan& P) {
+  const Options& o = h->opt;
+  P.blocked = !o.conv_direct;
+  P.chain = P.blocked && w.amax;
+  P.nslice = 1;
+  P.heads_cout = h->conv[kSpN - 1].cout;
+  bool wino[kSpN] = {};
+  for (int li = 1; li < kSpN; ++li) {     // the shape rules of the Winograd kernels and of their fp16 form
+    const ConvArgs a = conv_args(h, w, P, li, 0);
+    wino[li] = P.blocked && conv3x3_wino24_supported(a);
+    P.chain = P.chain && wino[li] && conv3x3_wino24h_supported(a);
+  }
+  for (int li = 1; li < kSpN; ++li) P.blocked = P.blocked && wino[li];
+  P.chain = P.chain && P.blocked;
+  if (det_only && P.blocked) {
+    P.heads_cout = 256;
+    const ConvArgs a = conv_args(h, w, P, kSpN - 1, 0);
+    if (!conv3x3_wino24_supported(a) || (P.chain && !conv3x3_wino24h_supported(a))) P.heads_cout = h->conv[kSpN - 1].cout;
+  }
+  if (P.chain) P.nslice = (w.B + kSlice - 1) / kSlice;
+  const bool pairs = P.chain && o.conv_f16 == 1;      // tile pairs where that fills the chip ("conv" = "wino_h": never) -- the same arithmetic, bit for bit
+  for (int r = P.nslice > 1 ? 0 : 1; r < 2; ++r) {
+    SpStep* st = P.steps[r];
+    for (int li = 0; li < kSpN; ++li) {
+      st[li] = SpStep{};
+      const ConvArgs a = conv_args(h, w, P, li, r ? P.nslice - 1 : 0);
+      if (li ? !wino[li] : o.conv_direct) st[li].form = ConvForm::Direct;      // (a layer the Winograd kernels reject, alone: the others keep them, on NHWC)
+      else if (li) st[li].form = !P.chain ? ConvForm::Wino : pairs && conv3x3_wino24p_preferred(a) ? ConvForm::WinoP : ConvForm::WinoH;
+      else st[li].form = !(P.chain && conv1ab_wino24h_supported(a)) ? ConvForm::C1 : pairs && conv1ab_wino24p_preferred(a) ? ConvForm::C1P : ConvForm::C1H;
+    }
+    for (int li = 0; li < kSpN; ++li) {
+      const bool swz = kSpLayers[li].swz && o.conv_swizzle != 0 && st[li].form == ConvForm::WinoP && st[li + 1].form == ConvForm::WinoP;
+      st[li].out_blocked = swz ? 2 : (P.blocked && !kSpLayers[li].last) ? 1 : 0;
+      if (li + 1 < kSpN) st[li + 1].in_blocked = st[li].out_blocked;
+    }
+  }
+}
+
+}  // namespace
 
 // ----------------------------------------------------------------------------- SuperPoint
 int sp_detect(imx_handle_t h, const float* img0, const float* img1, int split, int B, int H, int W, int32_t* counts_out,
@@ -32,137 +155,42 @@ int sp_detect(imx_handle_t h, const float* img0, const float* img1, int split, i
     WS(dense_, float, "sp.dense", (size_t)B * Hc * Wc * d * f);
     dense = dense_;
   }
-
-  // Activations between the Winograd layers are channel-blocked (B, C/8, H, W, 8) -- dense patch loads for the next layer
-  // (conv3x3_wino24.hip); the last 3x3 layer writes NHWC rows for the 1x1-conv GEMMs.  IMX_CONV=direct (or a layer the Winograd
-  // kernels reject) keeps NHWC everywhere: the direct kernel reads nothing else.
-  bool blocked = !h->opt.conv_direct, h_shapes = true;
-  {
-    const int hs[7] = {H2, H2, H4, H4, Hc, Hc, Hc}, ws_[7] = {W2, W2, W4, W4, Wc, Wc, Wc};
-    for (int i = 1; i < 8 && blocked; ++i) {
-      ConvArgs t{};
-      t.H = hs[i - 1]; t.W = ws_[i - 1]; t.Cin = h->conv[i].cin; t.Cout = h->conv[i].cout; t.wu24 = h->conv[i].wu24;
-      blocked = conv3x3_wino24_supported(t);
-      // the fp16-plane kernel's OWN predicate, in the same pre-pass (the chain used to be enabled on the fp32 kernel's
-      // predicate and a layer the fp16 kernel then rejected was a hard error; now the whole chain falls back to the fp32 kernels)
-      t.wuh = h->conv[i].wuh; t.u_scale_inv = h->conv[i].su_inv; t.amax_in = reinterpret_cast<const unsigned*>(h);      // (any non-null pointer: shape check only)
-      h_shapes = h_shapes && blocked && conv3x3_wino24h_supported(t);
+  // Round 6: NMS + threshold + remove_borders leave the detector as candidate BIT rows (20 words per 640-pixel row) and the keypoint kernels
+  // count / scatter from those -- the dense where(max_mask, scores, 0) map (a 157-MB write and two reads at C3) is only materialised for
+  // the debug tap, for "keypoints" = dense, and where the bit form does not apply (radius > 4 or 0, a negative threshold: there the
+  // suppressed zeros pass `> threshold`)
+  const bool kp_bits = nms_candidate_bits_supported(c.nms_radius, c.keypoint_threshold) && h->opt.keypoints != 0;
+  SpWork w{B, H, W, split, img0, img1, {a1, a2a, a2, a3a, a3, a4a, x4, hd}, nullptr};
+  const size_t amax_bytes = (size_t)((B + kSlice - 1) / kSlice) * kSpN * 256 * 4;
+  // (the table of the fp16-plane chain, 8 KB per slice, wherever options and weights allow the chain: the planner asks the shape rules
+  // with it; on shapes those reject it stays unused and is not zeroed)
+  if (!h->opt.conv_direct && conv_chain_h_ok(h) && h->opt.conv_f16 && !h->opt.mfma_f32) {      // (every 3x3 layer, and conv1a's plain output channels)
+    WS(am, unsigned, "sp.amax", amax_bytes);
+    w.amax = am;
+  }
+  SpPlan P;
+  plan_superpoint(h, w, det_only, P);
+  if (P.chain) HIP_OK(h, hipMemsetAsync(w.amax, 0, amax_bytes, s));
+  for (int li = 0; li < kSpN; ++li) {
+    const char* name = kSpLayers[li].last && P.heads_cout == 256 ? "convPa" : kSpLayers[li].name;
+    for (int sl = 0; sl < P.nslice; ++sl) {
+      const SpStep& st = P.steps[sl + 1 == P.nslice][li];
+      ConvArgs a = conv_args(h, w, P, li, sl);
+      a.in_blocked = st.in_blocked; a.out_blocked = st.out_blocked;
+      RUN(name, kConvLaunch[(int)st.form](a, s));
     }
   }
-  // "conv" = "wino": the layers after the first run their Winograd products on the fp16 matrix pipe (conv3x3_wino24h.hip).  Each needs an
-  // upper bound of |input| per image: one zeroed word per (layer, image), written by the PRODUCING layer's epilogue through atomicMax --
-  // the fused first layer starts the chain, so without it (conv = direct, shapes the Winograd kernels reject) the fp32 forms run
-  unsigned* amax = nullptr;
-  // ... and weights whose transformed values fit ONE power-of-two scale per layer: a layer whose typical output channel sits more than
-  // 2^14 below the largest |U| (a checkpoint with one runaway channel) would push that channel's weights under 2^-3 x 2^13 / 2^14 and
-  // lose the low plane -- the whole chain then runs the fp32-MFMA Winograd kernels ("conv" reports it through imx_timing_form)
-  const bool all_h = conv_chain_h_ok(h);      // (every 3x3 layer, and conv1a's plain output channels)
-  // The maxima live in 256 slots per layer (the kernels' LDS tables): a batch of more than 256 images runs its 3x3 layers in slices of
-  // 256 images, each with its own tables, so that an image's scales -- and with them its low-order bits -- never depend on which other
-  // images share the call (tests/test_gpu_superpoint.py: image b of a 260-image batch equals the same image alone).
-  constexpr int kSlice = 256;
-  const int nslice = (B + kSlice - 1) / kSlice;
-  if (blocked && all_h && h_shapes && h->opt.conv_f16 && !h->opt.mfma_f32) {
-    WS(am, unsigned, "sp.amax", (size_t)nslice * 8 * 256 * 4);          // one word per (slice, layer, image slot b % 256)
-    HIP_OK(h, hipMemsetAsync(am, 0, (size_t)nslice * 8 * 256 * 4, s));
-    amax = am;
-  }
-  int layer = 0;
-  // conv2a -> conv2b, conv3a -> conv3b, conv4a -> conv4b: the tensor between them is tile-swizzled (ConvArgs::out_blocked / in_blocked
-  // = 2) when BOTH layers run the pair kernel on this slice -- its stores are then 1 KB contiguous per instruction
-  // (conv3x3_wino24p.hip).  "conv_swizzle" = "off": never (the A/B switch of tools and tests; the results are bit-identical either way).
-  const bool swz_on = h->opt.conv_swizzle != 0;
-  auto swz_pair = [&](int li_prod, int hh, int ww, int nb) -> bool {
-    if (!amax || !swz_on || h->opt.conv_f16 != 1 || (li_prod != 1 && li_prod != 3 && li_prod != 5)) return false;
-    for (int k = 0; k < 2; ++k) {
-      const ConvW& cw = h->conv[li_prod + k];
-      ConvArgs t{};
-      t.B = nb; t.H = hh; t.W = ww; t.Cin = cw.cin; t.Cout = cw.cout; t.pool = (k == 1 && li_prod != 5) ? 1 : 0; t.relu = 1;
-      t.wu24 = cw.wu24; t.wuh = cw.wuh; t.u_scale_inv = cw.su_inv; t.amax_in = amax;
-      if (!conv3x3_wino24p_preferred(t)) return false;
-    }
-    return true;
-  };
-  auto conv = [&](const char* name, const ConvW& w, const float* in, float* out, int hh, int ww, bool pool, bool first, bool last = false) -> int {
-    const int li = layer++;
-    for (int sl = 0; sl < (amax ? nslice : 1); ++sl) {
-    ConvArgs a{};
-    const int b0 = amax ? sl * kSlice : 0, nb = amax ? std::min(kSlice, B - b0) : B;
-    const bool in_z = !first && swz_pair(li - 1, hh, ww, nb), out_z = !first && !pool && !last && swz_pair(li, hh, ww, nb);
-    const size_t ztile = (size_t)((hh + 7) / 8) * ((ww + 15) / 16) * 2048;       // floats per image and 16-channel block of a swizzled tensor
-    // (a slice's images are packed with their layout's own size; the SLICES of a tensor that may be swizzled are spaced by the padded
-    // size whatever each slice's layout is -- a short last slice can fall back to the blocked layout, and its region must not start
-    // inside the region of the slice before it)
-    const bool in_cand = li == 2 || li == 4 || li == 6, out_cand = li == 1 || li == 3 || li == 5;
-    const size_t in_img = in_cand ? ztile * (w.cin / 16) : (size_t)hh * ww * (first ? 1 : w.cin);
-    const size_t out_img = out_cand ? ztile * (w.cout / 16) : (size_t)(pool ? hh / 2 : hh) * (pool ? ww / 2 : ww) * w.cout;
-    if (amax) {
-      unsigned* am = amax + (size_t)sl * 8 * 256;
-      a.amax_out = last ? nullptr : am + (size_t)li * 256;
-      a.amax_in = li > 0 ? am + (size_t)(li - 1) * 256 : nullptr;
-      a.wuh = w.wuh; a.u_scale_inv = w.su_inv;
-      a.c1a_l1 = h->c1a_l1; a.c1a_bmax = h->c1a_bmax;
-    }
-    a.in_blocked = in_z ? 2 : (blocked && !first) ? 1 : 0;
-    a.out_blocked = out_z ? 2 : (blocked && !last) ? 1 : 0;
-    if (first) {                       // images below `split` come from img0, the others from img1: the slice's view of that
-      if (b0 >= split) { a.in = img1 + (size_t)(b0 - split) * in_img; a.in2 = nullptr; a.split = nb; }
-      else { a.in = in + (size_t)b0 * in_img; a.in2 = img1; a.split = split - b0; }
-    } else {
-      a.in = in + (size_t)b0 * in_img; a.in2 = nullptr; a.split = 0;
-    }
-    a.w = w.w; a.wu24 = w.wu24; a.bias = w.b; a.w1 = h->w1; a.b1 = h->b1; a.out = out + (size_t)b0 * out_img;
-    a.B = nb; a.H = hh; a.W = ww; a.Cin = w.cin; a.Cout = w.cout; a.relu = 1; a.pool = pool ? 1 : 0; a.first = first ? 1 : 0;
-    const bool fused1 = a.first && a.pool && !h->opt.conv_direct;
-    const bool wino = !a.first && !h->opt.conv_direct && conv3x3_wino24_supported(a);
-    const bool winoh = wino && amax && conv3x3_wino24h_supported(a);
-    if (amax && !fused1 && !winoh) return fail(h, "%s: the fp16-plane Winograd chain needs every layer to take part (internal)", name);
-    const bool fused1h = fused1 && amax && conv1ab_wino24h_supported(a);
-    // the fp16-plane layers: tile pairs with the positions split over two waves where that fills the chip (conv3x3_wino24p.hip: a U
-    // fragment serves two tiles), one tile per workgroup otherwise ("conv" = "wino_h": always) -- the same arithmetic, bit for bit
-    const bool winop = winoh && h->opt.conv_f16 == 1 && conv3x3_wino24p_preferred(a);
-    const bool fused1p = fused1h && h->opt.conv_f16 == 1 && conv1ab_wino24p_preferred(a);
-    if ((in_z || out_z) && !winop) return fail(h, "%s: a tile-swizzled tensor needs the pair kernel on both sides (internal)", name);
-    RUN(name, fused1p ? launch_conv1ab_wino24p(a, s) : fused1h ? launch_conv1ab_wino24h(a, s) : fused1 ? launch_conv1ab_wino24(a, s) : winop ? launch_conv3x3_wino24p(a, s) : winoh ? launch_conv3x3_wino24h(a, s) :
-              wino ? launch_conv3x3_wino24(a, s) : launch_conv3x3(a, s));
-    }
-    return 0;
-  };
-  if (conv("conv1ab_pool", h->conv[0], img0, a1, H, W, true, true)) return -1;
-  if (conv("conv2a", h->conv[1], a1, a2a, H2, W2, false, false)) return -1;
-  if (conv("conv2b_pool", h->conv[2], a2a, a2, H2, W2, true, false)) return -1;
-  if (conv("conv3a", h->conv[3], a2, a3a, H4, W4, false, false)) return -1;
-  if (conv("conv3b_pool", h->conv[4], a3a, a3, H4, W4, true, false)) return -1;
-  if (conv("conv4a", h->conv[5], a3, a4a, Hc, Wc, false, false)) return -1;
-  if (conv("conv4b", h->conv[6], a4a, x4, Hc, Wc, false, false)) return -1;
-  // det_only (imx_homography_adapt: only `semi` is consumed): the descriptor head is not run.  convPa | convDa share one launch whose
-  // Winograd weights are laid out by 64-channel output block, convPa's four blocks first, so a Cout = 256 view of the same buffers IS
-  // convPa alone; the direct form's [9][Cin][Cout] weights have no such prefix, so there (and where the Winograd kernels reject the
-  // narrower shape) the shared launch stays and only convDb is skipped.
-  ConvW heads = h->conv[7];
-  int hd_ld = 512;
-  if (det_only && blocked) {
-    ConvArgs t{};
-    t.B = std::min(B, kSlice); t.H = Hc; t.W = Wc; t.Cin = heads.cin; t.Cout = 256; t.wu24 = heads.wu24;
-    bool ok = conv3x3_wino24_supported(t);
-    if (ok && amax) { t.wuh = heads.wuh; t.u_scale_inv = heads.su_inv; t.amax_in = amax; ok = conv3x3_wino24h_supported(t); }
-    if (ok) { heads.cout = 256; hd_ld = 256; }
-  }
-  if (conv(hd_ld == 256 ? "convPa" : "convPaDa", heads, x4, hd, Hc, Wc, false, false, true)) return -1;
+  const bool blocked = P.blocked;
+  const int hd_ld = P.heads_cout;
   const int rows = B * Hc * Wc;
-  if (gemm(h, s, "convPb", h->pb, hd, hd_ld, 256, nullptr, 0, 0, nullptr, 0, semi, 65, rows, false)) return -1;
-  if (!det_only && gemm(h, s, "convDb", h->db, hd + 256, 512, 256, nullptr, 0, 0, nullptr, 0, dense, d, rows, false)) return -1;
+  if (gemm(h, s, "convPb", h->pb, gemm_args(h->pb, hd, hd_ld, 256, nullptr, 0, 0, nullptr, 0, semi, 65, rows, false))) return -1;
+  if (!det_only && gemm(h, s, "convDb", h->db, gemm_args(h->db, hd + 256, 512, 256, nullptr, 0, 0, nullptr, 0, dense, d, rows, false))) return -1;
   h->det_Hc = Hc; h->det_Wc = Wc;
   if (dense_only) { h->det_B = 0; h->nms_lazy.pending = false; return 0; }     // network only (imx_superpoint_dense)
   WS(smap, float, "sp.score_map", (size_t)B * H8 * W8 * f);
   WS(nms, float, "sp.nms", (size_t)B * H8 * W8 * f);
   RUN("softmax_shuffle", launch_softmax_shuffle(semi, 65, smap, B, Hc, Wc, s));
   WS(nms_scratch, unsigned, "sp.nms_scratch", nms_scratch_bytes(B, H8, W8, c.nms_radius));
-  // Round 6: NMS + threshold + remove_borders leave the detector as candidate BIT rows (20 words per 640-pixel row) and the keypoint kernels
-  // count / scatter from those -- the dense where(max_mask, scores, 0) map (a 157-MB write and two reads at C3) is only materialised for
-  // the debug tap, for "keypoints" = dense, and where the bit form does not apply (radius > 4 or 0, a negative threshold: there the
-  // suppressed zeros pass `> threshold`)
-  const bool kp_bits = nms_candidate_bits_supported(c.nms_radius, c.keypoint_threshold) && h->opt.keypoints != 0;
   if (kp_bits) RUN("nms", launch_nms_candidate_bits(smap, B, H8, W8, c.nms_radius, c.keypoint_threshold, c.remove_borders, s, nms_scratch));
   else RUN("nms", launch_nms(smap, nms, B, H8, W8, c.nms_radius, s, nms_scratch));
 
