@@ -39,7 +39,12 @@ class ImxConfig(ctypes.Structure):
     ]
 
 
+# libimx_sptrain.so (C ABI: include/imx_sptrain.h): the descriptor-training stages, on libimx.so's handles
+SPTRAIN_LIB_PATH = os.path.join(_HERE, "libimx_sptrain.so")
+SPTRAIN_EXPORTS = ("imx_warp_labels", "imx_erode_mask", "imx_detector_loss", "imx_desc_pairs", "imx_desc_loss_sparse")
+
 _lib = None
+_sptrain = None
 
 
 def load_library():
@@ -101,4 +106,26 @@ def load_library():
     for name in EXPORTS:
         getattr(lib, name)          # raises AttributeError if a declared symbol is missing
     _lib = lib
+    return lib
+
+
+def load_sptrain_library():
+    """Load libimx_sptrain.so (built beside libimx.so by the same make); libimx.so is loaded first: it makes the handles."""
+    global _sptrain
+    if _sptrain is not None:
+        return _sptrain
+    load_library()
+    if not os.path.exists(SPTRAIN_LIB_PATH):
+        raise RuntimeError(f"libimx_sptrain.so not found at {SPTRAIN_LIB_PATH}: build it with `make -C image-matching_amd/csrc`")
+    lib = ctypes.CDLL(SPTRAIN_LIB_PATH)
+    vp, i32, f32p = ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p
+    lib.imx_warp_labels.argtypes = [vp, f32p, vp, i32, i32, f32p, i32, i32, f32p, f32p, vp, vp]
+    lib.imx_erode_mask.argtypes = [vp, f32p, f32p, i32, i32, i32, i32, vp]
+    lib.imx_detector_loss.argtypes = [vp, f32p, f32p, f32p, i32, i32, i32, f32p, vp]
+    lib.imx_desc_loss_sparse.argtypes = [vp, f32p, f32p, i32, i32, i32, i32, f32p, vp, vp, i32, i32, ctypes.c_float, ctypes.c_float, i32,
+                                         f32p, f32p, vp, vp, vp]
+    lib.imx_desc_pairs.argtypes = [vp, f32p, i32, i32, i32, vp, vp, vp]
+    for name in SPTRAIN_EXPORTS:
+        getattr(lib, name)
+    _sptrain = lib
     return lib

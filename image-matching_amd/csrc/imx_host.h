@@ -1,5 +1,5 @@
 // imx_host.h -- internal header of the host units of libimx.so (imx_api.cpp, imx_options.cpp, imx_weights.cpp, imx_superpoint.cpp,
-// imx_superglue.cpp, imx_trainpairs.cpp): the handle, its weight sets and workspaces, the launch helpers, the weights-derived guards of the fp16-plane
+// imx_superglue.cpp, imx_trainpairs.cpp, imx_sptrain.cpp): the handle, its weight sets and workspaces, the launch helpers, the weights-derived guards of the fp16-plane
 // forms, and the stage functions the entry points call.  Nothing here is exported (hidden visibility; imx.map).
 #pragma once
 #include "../../include/imx.h"

@@ -448,4 +448,41 @@ struct LossArgs {
 };
 hipError_t launch_match_loss(const LossArgs& a, hipStream_t s);
 
+// ---------------------------------------------------------------- SuperPoint descriptor training (sptrain.hip)
+// ALLSS.points_to_2D / warpLabels (datasets/data_tools.py:36-54): the outputs are zero-filled by the launch itself
+struct WarpLabelsArgs {
+  const float* pts; const int* counts;      // (B,Kcap,2) (x,y); (B) counts or null = Kcap; rows past the count are never read
+  const float* mats;                        // (B,3,3) PIXEL-space matrices, or null = points_to_2D (no warp, no filter)
+  int B, Kcap, H, W;
+  float* labels; float* res;                // (B,H,W); (B,2,H,W) or null
+  int* owner;                               // (B,H,W) scratch: the highest point index on each pixel (needed when res is given)
+  int* flag;                                // bit 0: a point outside the image with mats null; may be null
+};
+hipError_t launch_warp_labels(const WarpLabelsArgs& a, hipStream_t s);
+// cv2.erode by getStructuringElement(MORPH_ELLIPSE, (2r, 2r)), 1 <= r <= kErodeMaxRadius, pixels outside the image take no part
+constexpr int kErodeMaxRadius = 128;
+hipError_t launch_erode_mask(const float* in, float* out, int B, int H, int W, int radius, hipStream_t s);
+// softmax-BCE detector loss over 8x8 cells: part = 2 detector_loss_blocks() doubles of scratch, out[2] = {loss, sum of cell masks}
+int detector_loss_blocks(int B, int Hc, int Wc);
+hipError_t launch_detector_loss(const float* semi, const float* labels, const float* mask, int B, int Hc, int Wc, double* part, float* out,
+                                hipStream_t s);
+// descriptor_loss_sparse (loss_functions/sparse_loss.py:98-174) for B images: indices in, losses out
+struct DescLossArgs {
+  const float* desc_a; const float* desc_b; // (B,d,Hc,Wc)
+  const float* hcell;                       // (B,3,3) homographies in cell coordinates
+  const int* choice; const int* nonmatch;   // (B,M) indices into the compacted pair list; (B,M,R) flat cell indices of side b
+  int B, d, Hc, Wc, M, R;
+  float lamda_d, margin;
+  int method2d;
+  float* ta; float* tb;                     // (B,Hc Wc,d) scratch: both maps cell-major
+  int* pairs; int* nvalid;                  // (B,Hc Wc,2), (B) scratch
+  float* partial;                           // (B,M,3) scratch
+  float* out; float* mean;                  // (B,5), (3)
+  int* pairs_out;                           // (B,Hc Wc,2) or null: the compacted (a, b) flat indices, -1 past n_valid
+  int* flag;                                // bit 0: a choice index past n_valid, bit 1: a non-match index outside the map; may be null
+};
+hipError_t launch_desc_loss_sparse(const DescLossArgs& a, hipStream_t s);
+// its first stage alone: hcell, B, Hc, Wc in; pairs and nvalid out (pairs_out and flag may be null, the other fields are not read)
+hipError_t launch_desc_pairs(const DescLossArgs& a, hipStream_t s);
+
 }  // namespace imx

@@ -43,6 +43,7 @@ class Engine:
 
     def __init__(self, sp_cfg, sg_cfg, device, sp_variant=L.SP_VARIANT_BN, align_corners=None):
         self.lib = L.load_library()
+        self.spt = L.load_sptrain_library()        # the descriptor-training stages (include/imx_sptrain.h), on the same handle
         if not torch.cuda.is_available():
             raise ImxError("image_matching_amd needs a ROCm GPU (torch.cuda.is_available() is False); "
                            "there is no CPU fallback on the product path")
@@ -498,6 +499,152 @@ class Engine:
                "descriptors0": desc[:B], "descriptors1": desc[B:], "counts0": counts[:B], "counts1": counts[B:]}
         out.update(self.gt_matches(out["keypoints0"], out["keypoints1"], M, counts[:B], counts[B:], radius))
         return out
+
+    # ------------------------------------------------------------------ SuperPoint descriptor training (Train_model_heatmap.py:83-314)
+    def _scaled(self, homographies, B, width, height, shift):
+        """inverse(trans) @ H @ trans with trans = [[2/width, 0, shift], [0, 2/height, shift], [0, 0, 1]] in fp32: the reference's torch
+        expression (homography_scaling_torch, utils/utils.py:586-589; scale_homography_torch, utils/homographies.py:121-125).  A host
+        tensor is multiplied on the host, as the reference does; a device tensor on the device (no synchronisation)."""
+        Hm = homographies if isinstance(homographies, torch.Tensor) else torch.as_tensor(np.asarray(homographies, dtype=np.float32))
+        Hm = Hm.type(torch.float32).reshape(-1, 3, 3)
+        if Hm.shape[0] != B:
+            raise ImxError(f"{Hm.shape[0]} homographies for a batch of {B}")
+        trans = torch.tensor([[2. / width, 0., shift], [0., 2. / height, shift], [0., 0., 1.]], dtype=torch.float32)
+        inv = torch.inverse(trans)
+        if Hm.device.type == "cpu":
+            out = torch.stack([inv @ m @ trans for m in Hm])           # one 2-D product chain per matrix, as the reference forms it
+        else:
+            out = inv.to(Hm.device) @ Hm @ trans.to(Hm.device)
+        return out.to(self.device, non_blocking=True).contiguous()
+
+    def _counts(self, counts, B, what):
+        if counts is None:
+            return None
+        c = counts if isinstance(counts, torch.Tensor) else torch.as_tensor(np.asarray(counts, dtype=np.int32))
+        c = c.to(self.device, torch.int32).contiguous()
+        if c.numel() != B:
+            raise ImxError(f"{what}: {c.numel()} counts for a batch of {B}")
+        return c
+
+    def warp_labels(self, pts, counts, homographies, H, W, want_res=True, pixel_space=False):
+        """warpLabels (datasets/data_tools.py:36-54) for B images, or ALLSS.points_to_2D with homographies=None.  pts (B,Kcap,2) (x, y),
+        counts (B) int32 or None, homographies (B,3,3) on [-1,1]^2 coordinates (scaled to pixels here by the reference's expression).
+        Returns (labels (B,H,W), res (B,2,H,W) or None, flag (1) int32 device word: non-zero = a point outside the image with
+        homographies=None).  Two points on one pixel: the higher point index writes the residual."""
+        pts = pts if isinstance(pts, torch.Tensor) else torch.as_tensor(np.asarray(pts, dtype=np.float32))
+        pts = pts.to(self.device, torch.float32).contiguous()
+        if pts.dim() != 3 or pts.shape[2] != 2:
+            raise ImxError(f"warp_labels: pts must be (B,Kcap,2), got {tuple(pts.shape)}")
+        B, K = int(pts.shape[0]), int(pts.shape[1])
+        counts = self._counts(counts, B, "warp_labels")
+        if homographies is None:
+            mats = None
+        elif pixel_space:                # the matrices already act on pixel coordinates: passed to the kernel as they are
+            mats = self._f32(homographies, (B, 3, 3), "warp_labels: homographies")
+        else:
+            mats = self._scaled(homographies, B, float(W), float(H), -1.)
+        labels = torch.empty(B, int(H), int(W), dtype=torch.float32, device=self.device)
+        res = torch.empty(B, 2, int(H), int(W), dtype=torch.float32, device=self.device) if want_res else None
+        flag = torch.empty(1, dtype=torch.int32, device=self.device)
+        self._check(self.spt.imx_warp_labels(self.handle, _ptr(pts), _ptr(counts), B, K, _ptr(mats), int(H), int(W), _ptr(labels), _ptr(res),
+                                             _ptr(flag), _stream(self.device)))
+        return labels, res, flag
+
+    def erode_mask(self, mask, radius):
+        """The margin of compute_valid_mask (utils/utils.py:449-452): cv2.erode by the (2r, 2r) elliptic element on (B,H,W) masks, as
+        restated in tests/sptrain_ref.py (parity with OpenCV itself is unpinned).  radius 0 copies."""
+        B, H, W = (int(v) for v in mask.shape)
+        mask = self._f32(mask, (B, H, W), "erode_mask: mask")
+        out = torch.empty_like(mask)
+        self._check(self.spt.imx_erode_mask(self.handle, _ptr(mask), _ptr(out), B, H, W, int(radius), _stream(self.device)))
+        return out
+
+    def detector_loss(self, semi, labels, mask, loss_type="softmax"):
+        """labels2Dto3D + getMasks + detector_loss (Train_model_heatmap.py:72-81) fused: semi (B,65,H/8,W/8), labels and mask (B,H,W)
+        or (B,1,H,W).  Returns a (2) device tensor {loss, sum of the cell masks}."""
+        if loss_type != "softmax":
+            raise NotImplementedError(f"detector_loss: only loss_type 'softmax' (the shipped yaml) is served, got {loss_type!r}")
+        B, C, Hc, Wc = (int(v) for v in semi.shape)
+        if C != 65:
+            raise ImxError(f"detector_loss: semi must have 65 channels, got {C}")
+        semi = self._f32(semi, (B, 65, Hc, Wc), "detector_loss: semi")
+        labels = self._f32(labels.reshape(B, Hc * 8, Wc * 8), (B, Hc * 8, Wc * 8), "detector_loss: labels")
+        mask = self._f32(mask.reshape(B, Hc * 8, Wc * 8), (B, Hc * 8, Wc * 8), "detector_loss: mask")
+        out = torch.empty(2, dtype=torch.float32, device=self.device)
+        self._check(self.spt.imx_detector_loss(self.handle, _ptr(semi), _ptr(labels), _ptr(mask), B, Hc * 8, Wc * 8, _ptr(out),
+                                               _stream(self.device)))
+        return out
+
+    def _cell_mats(self, homographies, B, Hc, Wc, cell_space):
+        if cell_space:                   # the matrices already act on cell coordinates: passed to the kernel as they are
+            return self._f32(homographies, (B, 3, 3), "homographies")
+        return self._scaled(homographies, B, float(Wc), float(Hc), -1.)
+
+    def desc_pairs(self, homographies, Hc, Wc, cell_space=False):
+        """The first stage of desc_loss_sparse alone (sparse_loss.py:118-124), for the caller's draws: homographies (B,3,3) on [-1,1]^2
+        -> (pairs (B,Hc Wc,2) int32: the compacted (a, b) flat cell indices, -1 past the count; n_valid (B) int32)."""
+        B = int(homographies.shape[0]) if hasattr(homographies, "shape") and len(homographies.shape) == 3 else 1
+        hcell = self._cell_mats(homographies, B, Hc, Wc, cell_space)
+        pairs = torch.empty(B, int(Hc) * int(Wc), 2, dtype=torch.int32, device=self.device)
+        n_valid = torch.empty(B, dtype=torch.int32, device=self.device)
+        self._check(self.spt.imx_desc_pairs(self.handle, _ptr(hcell), B, int(Hc), int(Wc), _ptr(pairs), _ptr(n_valid), _stream(self.device)))
+        return pairs, n_valid
+
+    def desc_loss_sparse(self, desc_a, desc_b, homographies, choice, nonmatch_b, lamda_d=250., margin=0.2, method="1d", want_pairs=False,
+                         cell_space=False):
+        """descriptor_loss_sparse (loss_functions/sparse_loss.py:98-174) for B images, indices in, losses out.  desc_{a,b} (B,d,Hc,Wc);
+        homographies (B,3,3) on [-1,1]^2 (scaled to cells here by scale_homography_torch's expression); choice (B,M) int32 indices into
+        the compacted pair list; nonmatch_b (B,M,R) int32 flat cell indices.  Returns dict: out (B,5) = {loss, lamda_d match, non_match,
+        num_hard_negatives, n_valid}, mean (3), flag (1) int32 [, pairs (B,Hc Wc,2) int32]."""
+        if method not in ("1d", "2d"):
+            raise ImxError(f"desc_loss_sparse: method must be '1d' or '2d', got {method!r}")
+        B, d, Hc, Wc = (int(v) for v in desc_a.shape)
+        desc_a = self._f32(desc_a, (B, d, Hc, Wc), "desc_loss_sparse: desc_a")
+        desc_b = self._f32(desc_b, (B, d, Hc, Wc), "desc_loss_sparse: desc_b")
+        hcell = self._cell_mats(homographies, B, Hc, Wc, cell_space)
+        choice = choice.to(self.device, torch.int32).contiguous()
+        nonmatch_b = nonmatch_b.to(self.device, torch.int32).contiguous()
+        if choice.dim() != 2 or choice.shape[0] != B or nonmatch_b.dim() != 3 or tuple(nonmatch_b.shape[:2]) != tuple(choice.shape):
+            raise ImxError(f"desc_loss_sparse: choice {tuple(choice.shape)} must be (B,M) and nonmatch_b {tuple(nonmatch_b.shape)} (B,M,R)")
+        M, R = int(choice.shape[1]), int(nonmatch_b.shape[2])
+        res = {"out": torch.empty(B, 5, dtype=torch.float32, device=self.device), "mean": torch.empty(3, dtype=torch.float32, device=self.device),
+               "flag": torch.empty(1, dtype=torch.int32, device=self.device)}
+        if want_pairs:
+            res["pairs"] = torch.empty(B, Hc * Wc, 2, dtype=torch.int32, device=self.device)
+        self._check(self.spt.imx_desc_loss_sparse(self.handle, _ptr(desc_a), _ptr(desc_b), B, d, Hc, Wc, _ptr(hcell), _ptr(choice), _ptr(nonmatch_b),
+                                                  M, R, float(lamda_d), float(margin), 1 if method == "1d" else 2, _ptr(res["out"]),
+                                                  _ptr(res["mean"]), _ptr(res.get("pairs")), _ptr(res["flag"]), _stream(self.device)))
+        return res
+
+    def sp_train_losses(self, images, pts, counts, homographies, inv_homographies, choice, nonmatch_b, erosion_radius=0, lamda_d=250.,
+                        margin=0.2, method="2d", lambda_loss=1.):
+        """One validation batch of Train_model_heatmap.py:83-314 on one stream without a host synchronisation: the warped images
+        (inv_warp_image, bilinear) and their valid masks (nearest, eroded), both label maps, the dense SuperPoint on the 2B images, both
+        detector losses and the sparse descriptor loss.  images (B,1,H,W) or (B,H,W); pts (B,Kcap,2) / counts (B): the pseudo-labels;
+        homographies / inv_homographies (B,3,3) on [-1,1]^2 as ALLSS hands them out; choice (B,M) / nonmatch_b (B,M,R): the caller's draws
+        (see desc_loss_sparse).  Returns a dict of device tensors: loss, loss_det, loss_det_warp, loss_desc, positive_dist, negative_dist
+        (scalars), desc (the desc_loss_sparse dict), labels_2D, warped_labels, warped_res, warped_img, valid_mask, warped_valid_mask, semi,
+        semi_warp, coarse_desc, coarse_desc_warp, flag (of the unwarped label map)."""
+        B, H, W = int(images.shape[0]), int(images.shape[-2]), int(images.shape[-1])
+        img = self._f32(images.reshape(B, H, W), (B, H, W), "sp_train_losses: images")
+        inv = self._f32(inv_homographies, (B, 3, 3), "sp_train_losses: inv_homographies")
+        x = torch.empty(2 * B, 1, H, W, dtype=torch.float32, device=self.device)
+        x[:B, 0].copy_(img)
+        st = _stream(self.device)
+        self._check(self.lib.imx_warp_homography(self.handle, _ptr(img), 0, B, H, W, _ptr(inv), 0, _ptr(x[B:]), st))
+        warped_mask = self.erode_mask(self.warp_homography((H, W), inv, mode="nearest"), erosion_radius)
+        valid_mask = torch.ones(B, H, W, dtype=torch.float32, device=self.device)     # ALLSS: compute_valid_mask under the identity
+        labels, _, flag = self.warp_labels(pts, counts, None, H, W, want_res=False)
+        wlabels, wres, _ = self.warp_labels(pts, counts, homographies, H, W)
+        semi, desc = self.superpoint_dense(x)
+        det = self.detector_loss(semi[:B], labels, valid_mask)
+        det_w = self.detector_loss(semi[B:], wlabels, warped_mask)
+        dl = self.desc_loss_sparse(desc[:B], desc[B:], homographies, choice, nonmatch_b, lamda_d=lamda_d, margin=margin, method=method)
+        loss = det[0] + det_w[0] + float(lambda_loss) * dl["mean"][0]
+        return {"loss": loss, "loss_det": det[0], "loss_det_warp": det_w[0], "loss_desc": dl["mean"][0], "positive_dist": dl["mean"][1],
+                "negative_dist": dl["mean"][2], "desc": dl, "labels_2D": labels, "warped_labels": wlabels, "warped_res": wres,
+                "warped_img": x[B:], "valid_mask": valid_mask, "warped_valid_mask": warped_mask, "semi": semi[:B], "semi_warp": semi[B:],
+                "coarse_desc": desc[:B], "coarse_desc_warp": desc[B:], "flag": flag}
 
     # ------------------------------------------------------------------ kernel-form options (include/imx.h: imx_set_option)
     def set_option(self, key, value):
