@@ -485,4 +485,28 @@ hipError_t launch_desc_loss_sparse(const DescLossArgs& a, hipStream_t s);
 // its first stage alone: hcell, B, Hc, Wc in; pairs and nvalid out (pairs_out and flag may be null, the other fields are not read)
 hipError_t launch_desc_pairs(const DescLossArgs& a, hipStream_t s);
 
+// ---------------------------------------------------------------- gradients of the two SuperPoint training losses (spgrad.hip)
+// d out[0] / d semi after launch_detector_loss wrote out[2]: grad (B,65,Hc,Wc), gout one float on the device or null = 1
+hipError_t launch_detector_loss_grad(const float* semi, const float* labels, const float* mask, int B, int Hc, int Wc, const float* out,
+                                     const float* gout, float* grad, hipStream_t s);
+// d mean[0] / d desc_{a,b} after launch_desc_loss_sparse(f) ran on the same stream.  Per image E = M K entries, K = 2 T + 1 + R slots per
+// match (T = 1 tap for '1d', 4 for '2d'), over 2 N destinations (a's cells, then b's): DESIGN.md section 12.
+struct DescGradArgs {
+  DescLossArgs f;                           // the forward's arguments, its scratch filled
+  const float* gout;                        // one float or null = 1
+  float* grad_a; float* grad_b;             // (B,d,Hc,Wc)
+  float* xm; float* ym; float* an;          // (B,M,d) scratch: the match vectors of a and b, the sum of a match's active non-match rows
+  int* ia;                                  // (B,M) scratch: the a cell of match m, -1 where it takes no part
+  int* keys; float* coef;                   // (B,E) scratch: destination (or -1) and coefficient of every entry
+  int* hist;                                // (B,S,2N) scratch: per-segment counts, then per-segment cursors
+  int* offs;                                // (B,2N+1) scratch: where each destination's list begins
+  int* list;                                // (B,E) scratch: the entries grouped by destination, ascending inside each
+  float* gt;                                // (B,2N,d) scratch: the gradient cell-major
+  int S, seg;                               // segments per image and entries per segment (desc_grad_segments)
+};
+constexpr int kDescGradMaxSegments = 64;
+inline int desc_grad_slots(int R, int method2d) { return 2 * (method2d ? 4 : 1) + 1 + R; }
+inline int desc_grad_segments(long E) { long S = (E + 4095) / 4096; return (int)(S < 1 ? 1 : S > kDescGradMaxSegments ? kDescGradMaxSegments : S); }
+hipError_t launch_desc_loss_sparse_grad(const DescGradArgs& g, hipStream_t s);
+
 }  // namespace imx

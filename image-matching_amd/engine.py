@@ -646,6 +646,98 @@ class Engine:
                 "warped_img": x[B:], "valid_mask": valid_mask, "warped_valid_mask": warped_mask, "semi": semi[:B], "semi_warp": semi[B:],
                 "coarse_desc": desc[:B], "coarse_desc_warp": desc[B:], "flag": flag}
 
+    # ------------------------------------------------------------------ gradients of the two training losses (include/imx_spgrad.h)
+    @property
+    def spg(self):
+        """libimx_spgrad.so, loaded on the first use of a gradient method"""
+        if getattr(self, "_spg", None) is None:
+            self._spg = L.load_spgrad_library()
+        return self._spg
+
+    def _gout(self, gout):
+        if gout is None:
+            return None
+        if not isinstance(gout, torch.Tensor):                           # a fill kernel on the stream: no host-to-device copy, no wait
+            return torch.full((1,), float(gout), dtype=torch.float32, device=self.device)
+        return gout.to(self.device, torch.float32).reshape(1).contiguous()
+
+    def detector_loss_grad(self, semi, labels, mask, gout=None, loss_type="softmax"):
+        """detector_loss and its derivative with respect to semi in one call: returns (out (2) = {loss, sum of the cell masks},
+        grad_semi (B,65,H/8,W/8) = gout d loss / d semi).  gout: a device scalar (or a number), None = 1.  The derivative is that of the
+        conditioned form the library evaluates (include/imx_spgrad.h)."""
+        if loss_type != "softmax":
+            raise NotImplementedError(f"detector_loss_grad: only loss_type 'softmax' (the shipped yaml) is served, got {loss_type!r}")
+        B, C, Hc, Wc = (int(v) for v in semi.shape)
+        if C != 65:
+            raise ImxError(f"detector_loss_grad: semi must have 65 channels, got {C}")
+        semi = self._f32(semi, (B, 65, Hc, Wc), "detector_loss_grad: semi")
+        labels = self._f32(labels.reshape(B, Hc * 8, Wc * 8), (B, Hc * 8, Wc * 8), "detector_loss_grad: labels")
+        mask = self._f32(mask.reshape(B, Hc * 8, Wc * 8), (B, Hc * 8, Wc * 8), "detector_loss_grad: mask")
+        gout = self._gout(gout)
+        out = torch.empty(2, dtype=torch.float32, device=self.device)
+        grad = torch.empty(B, 65, Hc, Wc, dtype=torch.float32, device=self.device)
+        self._check(self.spg.imx_detector_loss_grad(self.handle, _ptr(semi), _ptr(labels), _ptr(mask), B, Hc * 8, Wc * 8, _ptr(gout), _ptr(out),
+                                                    _ptr(grad), _stream(self.device)))
+        return out, grad
+
+    def desc_loss_sparse_grad(self, desc_a, desc_b, homographies, choice, nonmatch_b, lamda_d=250., margin=0.2, method="1d", gout=None,
+                              want_pairs=False, cell_space=False):
+        """desc_loss_sparse and the derivative of its batch-mean total (mean[0]) with respect to both descriptor maps in one call.  The
+        arguments of desc_loss_sparse plus gout (a device scalar or a number, None = 1).  Returns its dict plus grad_a and grad_b
+        (B,d,Hc,Wc).  Bit 2 of flag: an image without a valid pair (zero gradients)."""
+        if method not in ("1d", "2d"):
+            raise ImxError(f"desc_loss_sparse_grad: method must be '1d' or '2d', got {method!r}")
+        B, d, Hc, Wc = (int(v) for v in desc_a.shape)
+        desc_a = self._f32(desc_a, (B, d, Hc, Wc), "desc_loss_sparse_grad: desc_a")
+        desc_b = self._f32(desc_b, (B, d, Hc, Wc), "desc_loss_sparse_grad: desc_b")
+        hcell = self._cell_mats(homographies, B, Hc, Wc, cell_space)
+        choice = choice.to(self.device, torch.int32).contiguous()
+        nonmatch_b = nonmatch_b.to(self.device, torch.int32).contiguous()
+        if choice.dim() != 2 or choice.shape[0] != B or nonmatch_b.dim() != 3 or tuple(nonmatch_b.shape[:2]) != tuple(choice.shape):
+            raise ImxError(f"desc_loss_sparse_grad: choice {tuple(choice.shape)} must be (B,M) and nonmatch_b {tuple(nonmatch_b.shape)} (B,M,R)")
+        M, R = int(choice.shape[1]), int(nonmatch_b.shape[2])
+        gout = self._gout(gout)
+        res = {"out": torch.empty(B, 5, dtype=torch.float32, device=self.device), "mean": torch.empty(3, dtype=torch.float32, device=self.device),
+               "flag": torch.empty(1, dtype=torch.int32, device=self.device),
+               "grad_a": torch.empty(B, d, Hc, Wc, dtype=torch.float32, device=self.device),
+               "grad_b": torch.empty(B, d, Hc, Wc, dtype=torch.float32, device=self.device)}
+        if want_pairs:
+            res["pairs"] = torch.empty(B, Hc * Wc, 2, dtype=torch.int32, device=self.device)
+        self._check(self.spg.imx_desc_loss_sparse_grad(self.handle, _ptr(desc_a), _ptr(desc_b), B, d, Hc, Wc, _ptr(hcell), _ptr(choice),
+                                                       _ptr(nonmatch_b), M, R, float(lamda_d), float(margin), 1 if method == "1d" else 2,
+                                                       _ptr(gout), _ptr(res["out"]), _ptr(res["mean"]), _ptr(res.get("pairs")), _ptr(res["flag"]),
+                                                       _ptr(res["grad_a"]), _ptr(res["grad_b"]), _stream(self.device)))
+        return res
+
+    def sp_train_loss_grads(self, images, pts, counts, homographies, inv_homographies, choice, nonmatch_b, erosion_radius=0, lamda_d=250.,
+                            margin=0.2, method="2d", lambda_loss=1.):
+        """sp_train_losses (same arguments, same stages, same stream, no host synchronisation) with the two losses run as
+        value-and-gradient calls: returns its dict, bit-identical, plus grad_semi, grad_semi_warp (B,65,H/8,W/8), grad_desc and
+        grad_desc_warp (B,d,H/8,W/8): d loss / d of what the network emitted, loss = loss_det + loss_det_warp + lambda_loss loss_desc."""
+        B, H, W = int(images.shape[0]), int(images.shape[-2]), int(images.shape[-1])
+        img = self._f32(images.reshape(B, H, W), (B, H, W), "sp_train_loss_grads: images")
+        inv = self._f32(inv_homographies, (B, 3, 3), "sp_train_loss_grads: inv_homographies")
+        x = torch.empty(2 * B, 1, H, W, dtype=torch.float32, device=self.device)
+        x[:B, 0].copy_(img)
+        st = _stream(self.device)
+        self._check(self.lib.imx_warp_homography(self.handle, _ptr(img), 0, B, H, W, _ptr(inv), 0, _ptr(x[B:]), st))
+        warped_mask = self.erode_mask(self.warp_homography((H, W), inv, mode="nearest"), erosion_radius)
+        valid_mask = torch.ones(B, H, W, dtype=torch.float32, device=self.device)
+        labels, _, flag = self.warp_labels(pts, counts, None, H, W, want_res=False)
+        wlabels, wres, _ = self.warp_labels(pts, counts, homographies, H, W)
+        semi, desc = self.superpoint_dense(x)
+        det, g_semi = self.detector_loss_grad(semi[:B], labels, valid_mask)
+        det_w, g_semi_w = self.detector_loss_grad(semi[B:], wlabels, warped_mask)
+        dl = self.desc_loss_sparse_grad(desc[:B], desc[B:], homographies, choice, nonmatch_b, lamda_d=lamda_d, margin=margin, method=method,
+                                        gout=float(lambda_loss))
+        g_a, g_b = dl.pop("grad_a"), dl.pop("grad_b")
+        loss = det[0] + det_w[0] + float(lambda_loss) * dl["mean"][0]
+        return {"loss": loss, "loss_det": det[0], "loss_det_warp": det_w[0], "loss_desc": dl["mean"][0], "positive_dist": dl["mean"][1],
+                "negative_dist": dl["mean"][2], "desc": dl, "labels_2D": labels, "warped_labels": wlabels, "warped_res": wres,
+                "warped_img": x[B:], "valid_mask": valid_mask, "warped_valid_mask": warped_mask, "semi": semi[:B], "semi_warp": semi[B:],
+                "coarse_desc": desc[:B], "coarse_desc_warp": desc[B:], "flag": flag, "grad_semi": g_semi, "grad_semi_warp": g_semi_w,
+                "grad_desc": g_a, "grad_desc_warp": g_b}
+
     # ------------------------------------------------------------------ kernel-form options (include/imx.h: imx_set_option)
     def set_option(self, key, value):
         """'mfma' = 'x3' | 'f32', 'latency_forms' = 'auto' | 'off' | 'on' | 'unfused', 'conv' = 'wino' | 'wino_h' | 'wino32' | 'direct',

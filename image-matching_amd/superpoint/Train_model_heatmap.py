@@ -83,9 +83,10 @@ class Train_model_heatmap(object):
         counts = torch.clamp(torch.cat([r[1] for r in rows]), max=cap)
         return eng.warp_labels(pts, counts, None, H, W, want_res=False)[0]
 
-    def val_sample(self, sample, generator=None):
+    def val_sample(self, sample, generator=None, grads=False):
         """One validation batch: `sample` is ALLSS.batch(indices).  Returns the scalar dictionary of train_val_sample (:251-259, :305-309)
-        as 0-d device tensors."""
+        as 0-d device tensors.  grads=True: the losses run as value-and-gradient calls (Engine.sp_train_loss_grads) and the dictionary
+        also holds the L2 norms of d loss / d semi, semi_warp, desc and desc_warp."""
         if self.net is None:
             self.loadModel()
         eng = self.net._shared.get_engine([L.NET_SUPERPOINT])
@@ -94,11 +95,14 @@ class Train_model_heatmap(object):
         B, H, W = images.shape[0], images.shape[-2], images.shape[-1]
         choice, non = sptrain.draw(eng, sample["homographies"], H // 8, W // 8, int(p.get("num_matching_attempts", 1000)),
                                    int(p.get("num_masked_non_matches_per_match", 10)), generator)
-        out = eng.sp_train_losses(images, sample["pts"], sample["counts"], sample["homographies"], sample["inv_homographies"], choice, non,
-                                  erosion_radius=sample.get("valid_border_margin", 0), lamda_d=p.get("lamda_d", 250), method=p.get("method", "1d"),
-                                  lambda_loss=self.config["model"].get("lambda_loss", 1))
+        losses = eng.sp_train_loss_grads if grads else eng.sp_train_losses
+        out = losses(images, sample["pts"], sample["counts"], sample["homographies"], sample["inv_homographies"], choice, non,
+                     erosion_radius=sample.get("valid_border_margin", 0), lamda_d=p.get("lamda_d", 250), method=p.get("method", "1d"),
+                     lambda_loss=self.config["model"].get("lambda_loss", 1))
         pred = self.heatmap_to_nms(eng, eng.superpoint_heatmap(images.reshape(B, 1, H, W).to(eng.device, torch.float32)))
         self.scalar_dict = {k: out[k] for k in ("loss", "loss_det", "loss_det_warp", "positive_dist", "negative_dist")}
         self.scalar_dict.update(self.batch_precision_recall(pred, out["labels_2D"]))
+        if grads:
+            self.scalar_dict.update({k + "_norm": out[k].norm() for k in ("grad_semi", "grad_semi_warp", "grad_desc", "grad_desc_warp")})
         self.outputs = out
         return self.scalar_dict

@@ -5,7 +5,8 @@ N synthetic images whose pseudo-labels come from homographic adaptation (export_
 
     python superpoint_validate_descriptor.py --synthetic 2 --size 120 160
 
-There is no backward pass: training itself stays with the reference."""
+--grads prints the norms of the loss gradients at the network's outputs as well (include/imx_spgrad.h).  The backward of the network's
+own layers is not here: training itself stays with the reference, which may take those cotangents."""
 import argparse
 import json
 
@@ -31,6 +32,8 @@ if __name__ == '__main__':
     parser.add_argument("--output_dir", type=str, default='Results/ALLSS/')
     parser.add_argument("--synthetic", type=int, default=0, help="validate on N synthetic images instead of datasets/ALLSS/val")
     parser.add_argument("--size", type=int, nargs=2, default=None, help="H W of the synthetic images (default: preprocessing.resize)")
+    parser.add_argument("--grads", action="store_true",
+                        help="run the losses as value-and-gradient calls and print the L2 norms of d loss / d semi, semi_warp, desc, desc_warp too")
     args = parser.parse_args()
 
     from image_matching_amd import homoadapt, synth
@@ -62,7 +65,7 @@ if __name__ == '__main__':
     bs = config['model']['eval_batch_size']
     totals, batches = {}, 0
     for i0 in range(0, len(val_set), bs):
-        scalars = agent.val_sample(val_set.batch(range(i0, min(i0 + bs, len(val_set)))))
+        scalars = agent.val_sample(val_set.batch(range(i0, min(i0 + bs, len(val_set)))), grads=args.grads)
         for k, v in scalars.items():
             totals[k] = totals.get(k, 0.0) + float(v)
         batches += 1
