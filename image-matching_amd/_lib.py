@@ -45,10 +45,14 @@ SPTRAIN_EXPORTS = ("imx_warp_labels", "imx_erode_mask", "imx_detector_loss", "im
 # libimx_spgrad.so (C ABI: include/imx_spgrad.h): the two training losses as value-and-gradient calls, on libimx.so's handles
 SPGRAD_LIB_PATH = os.path.join(_HERE, "libimx_spgrad.so")
 SPGRAD_EXPORTS = ("imx_detector_loss_grad", "imx_desc_loss_sparse_grad")
+# libimx_otgrad.so (C ABI: include/imx_otgrad.h): the SuperGlue match loss through the unrolled Sinkhorn, value-and-gradient, on libimx.so's handles
+OTGRAD_LIB_PATH = os.path.join(_HERE, "libimx_otgrad.so")
+OTGRAD_EXPORTS = ("imx_ot_match_loss_grad",)
 
 _lib = None
 _sptrain = None
 _spgrad = None
+_otgrad = None
 
 
 def load_library():
@@ -151,4 +155,21 @@ def load_spgrad_library():
     for name in SPGRAD_EXPORTS:
         getattr(lib, name)
     _spgrad = lib
+    return lib
+
+
+def load_otgrad_library():
+    """Load libimx_otgrad.so (built beside libimx.so by the same make); libimx.so is loaded first: it makes the handles."""
+    global _otgrad
+    if _otgrad is not None:
+        return _otgrad
+    load_library()
+    if not os.path.exists(OTGRAD_LIB_PATH):
+        raise RuntimeError(f"libimx_otgrad.so not found at {OTGRAD_LIB_PATH}: build it with `make -C image-matching_amd/csrc`")
+    lib = ctypes.CDLL(OTGRAD_LIB_PATH)
+    vp, i32, f32p = ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p
+    lib.imx_ot_match_loss_grad.argtypes = [vp, i32, f32p, i32, i32, vp, vp, f32p, i32, vp, vp, i32, f32p, f32p, f32p, f32p, vp, vp]
+    for name in OTGRAD_EXPORTS:
+        getattr(lib, name)
+    _otgrad = lib
     return lib

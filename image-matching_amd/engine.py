@@ -738,6 +738,51 @@ class Engine:
                 "coarse_desc": desc[:B], "coarse_desc_warp": desc[B:], "flag": flag, "grad_semi": g_semi, "grad_semi_warp": g_semi_w,
                 "grad_desc": g_a, "grad_desc_warp": g_b}
 
+    # ------------------------------------------------------------------ the SuperGlue match loss and its gradient (include/imx_otgrad.h)
+    @property
+    def otg(self):
+        """libimx_otgrad.so, loaded on the first use"""
+        if getattr(self, "_otg", None) is None:
+            self._otg = L.load_otgrad_library()
+        return self._otg
+
+    def ot_match_loss_grad(self, scores, bin_score, all_matches, n_all, iters, n0=None, n1=None, gout=None, want_grad=True):
+        """The objective of superglue/models/superglue_train.py:271-299 on a score matrix, with its derivative through the unrolled
+        Sinkhorn: scores (B,N0,N1) fp32, bin_score a one-element fp32 device tensor (or a number), all_matches (B,2,L) int64 and n_all (B)
+        int32 as gt_matches writes them, n0 / n1 (B) int32 counts or None = all, gout (B) upstream cotangents or None = 1.  Returns
+        dict: loss (B), flag (B) int32 (bit 0: a listed index outside the coupling matrix) and, unless want_grad is False, grad_scores
+        (B,N0,N1) (0 past the counts) and grad_bin (B).  No host synchronisation."""
+        dev = self.device
+        if scores.dim() != 3:
+            raise ImxError(f"ot_match_loss_grad: scores must be (B,N0,N1), got {tuple(scores.shape)}")
+        B, N0, N1 = (int(v) for v in scores.shape)
+        scores = self._f32(scores, (B, N0, N1), "ot_match_loss_grad: scores")
+        if not isinstance(bin_score, torch.Tensor):
+            bin_score = torch.full((1,), float(bin_score), dtype=torch.float32, device=dev)
+        if bin_score.numel() != 1:
+            raise ImxError(f"ot_match_loss_grad: bin_score must hold one element, got {tuple(bin_score.shape)}")
+        bin_score = bin_score.detach().to(dev, torch.float32).reshape(1).contiguous()
+        all_matches = all_matches.to(dev, torch.int64).contiguous()
+        if all_matches.dim() != 3 or all_matches.shape[0] != B or all_matches.shape[1] != 2:
+            raise ImxError(f"ot_match_loss_grad: all_matches must be (B,2,L) with B = {B}, got {tuple(all_matches.shape)}")
+        Lc = int(all_matches.shape[2])
+        n_all = self._counts(n_all, B, "ot_match_loss_grad: n_all")
+        n0, n1 = self._counts(n0, B, "ot_match_loss_grad: n0"), self._counts(n1, B, "ot_match_loss_grad: n1")
+        if n_all is None:
+            raise ImxError("ot_match_loss_grad: n_all is required")
+        if gout is not None:
+            gout = gout.to(dev, torch.float32).contiguous()
+            if gout.numel() != B:
+                raise ImxError(f"ot_match_loss_grad: {gout.numel()} cotangents for a batch of {B}")
+        res = {"loss": torch.empty(B, dtype=torch.float32, device=dev), "flag": torch.empty(B, dtype=torch.int32, device=dev)}
+        if want_grad:
+            res["grad_scores"] = torch.empty(B, N0, N1, dtype=torch.float32, device=dev)
+            res["grad_bin"] = torch.empty(B, dtype=torch.float32, device=dev)
+        self._check(self.otg.imx_ot_match_loss_grad(self.handle, B, _ptr(scores), N0, N1, _ptr(n0), _ptr(n1), _ptr(bin_score), int(iters),
+                                                    _ptr(all_matches), _ptr(n_all), Lc, _ptr(gout), _ptr(res["loss"]),
+                                                    _ptr(res.get("grad_scores")), _ptr(res.get("grad_bin")), _ptr(res["flag"]), _stream(dev)))
+        return res
+
     # ------------------------------------------------------------------ kernel-form options (include/imx.h: imx_set_option)
     def set_option(self, key, value):
         """'mfma' = 'x3' | 'f32', 'latency_forms' = 'auto' | 'off' | 'on' | 'unfused', 'conv' = 'wino' | 'wino_h' | 'wino32' | 'direct',

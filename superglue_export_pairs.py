@@ -7,9 +7,11 @@ Per image of <image_path>/train: a random perspective warp, SuperPoint on both i
 (image0, image1, M, keypoints0/1, scores0/1, descriptors0/1 (d,N), matches (2,n), all_matches (2,n_all)).  With SuperGlue weights
 (--pretrain_weights indoor | outdoor, or --superglue_checkpoint <file with a 'net' entry>) the same pass scores them: mean loss
 (superglue_train.py:289-299), precision and recall of matches0 against the ground truth.  There is no backward pass here: train
-with the reference's module on the exported pairs, validate checkpoints here.
+with the reference's module on the exported pairs, validate checkpoints here.  --grads prints, beside the loss, the norms of its gradient at the
+score matrix and at bin_score through the unrolled Sinkhorn (include/imx_otgrad.h), on the forward's own score matrix copied out of the
+workspace (the debug tap 'scores_in': a host round trip, this is a validation tool); the backward of the network's layers is PyTorch's.
 
-The SuperPoint and SuperGlue flags are those of superpoint_glue_train.py; --out_dir, --batch, --seed, --superglue_checkpoint and
+The SuperPoint and SuperGlue flags are those of superpoint_glue_train.py; --out_dir, --batch, --seed, --superglue_checkpoint, --grads and
 --synthetic N (N synthetic images, synthetic weights, no dataset) are not in the reference."""
 import argparse
 import os
@@ -43,6 +45,7 @@ def build_parser():
     parser.add_argument('--batch', type=int, default=16, help='samples per pass')
     parser.add_argument('--seed', type=int, default=0, help='seed of the warp sampler')
     parser.add_argument('--synthetic', type=int, default=0, help='export this many synthetic images (no dataset, synthetic weights)')
+    parser.add_argument('--grads', action='store_true', help='print the norms of d loss / d scores and d loss / d bin_score beside the loss')
     return parser
 
 
@@ -103,6 +106,7 @@ def main(argv=None):
     os.makedirs(opt.out_dir, exist_ok=True)
     H, W = opt.resize[1], opt.resize[0]
     losses, stats, written, skipped = [], np.zeros(3, np.int64), 0, 0
+    grad_losses, grad_norms, grad_bins = [], [], []
     for start in range(0, len(ds), opt.batch):
         out = ds.batch(range(start, min(start + opt.batch, len(ds))))
         tensors = {k: v for k, v in out.items() if isinstance(v, torch.Tensor)}
@@ -112,6 +116,12 @@ def main(argv=None):
                                         out['keypoints1'], out['scores1'], out['descriptors1'].transpose(1, 2), (H, W),
                                         n0=out['counts0'], n1=out['counts1'])
             tensors['loss'], tensors['stats'] = eng.match_loss(out['all_matches'], out['n_all'], m0, out['gt0'])
+            if opt.grads:
+                scores = torch.from_numpy(eng.fetch('scores_in')).to(device)     # (B,N0p,N1p): the forward's scores, padding never read
+                g = eng.ot_match_loss_grad(scores, float(superglue.state_dict()['bin_score']), out['all_matches'], out['n_all'],
+                                           opt.sinkhorn_iterations, n0=out['counts0'], n1=out['counts1'])
+                tensors['grad_loss'], tensors['grad_bin'] = g['loss'], g['grad_bin']
+                tensors['grad_norm'] = g['grad_scores'].flatten(1).norm(dim=1)
         torch.cuda.synchronize()
         host = {k: v.cpu().numpy() for k, v in tensors.items()}
         write_samples(opt.out_dir, out, host)
@@ -121,11 +131,18 @@ def main(argv=None):
         if superglue is not None:
             losses += list(host['loss'][keep])
             stats += host['stats'][keep].sum(0)
+            if opt.grads:
+                grad_losses += list(host['grad_loss'][keep])
+                grad_norms += list(host['grad_norm'][keep])
+                grad_bins += list(host['grad_bin'][keep])
     print(f"wrote {written} samples to {opt.out_dir} ({skipped} without keypoints on a side)")
     if superglue is not None and losses:
         n_gt, n_pred, n_ok = (int(v) for v in stats)
         print(f"validation over {len(losses)} pairs: loss {float(np.mean(losses)):.4f}  precision {n_ok / max(n_pred, 1):.4f}  recall {n_ok / max(n_gt, 1):.4f}  "
               f"({n_ok} correct of {n_pred} predicted, {n_gt} ground-truth matches)")
+        if opt.grads:
+            print(f"gradients over {len(grad_losses)} pairs: loss {float(np.mean(grad_losses)):.4f} (the recorded Sinkhorn of imx_ot_match_loss_grad)  "
+                  f"mean |d loss / d scores| {float(np.mean(grad_norms)):.6f}  mean d loss / d bin_score {float(np.mean(grad_bins)):.6f}")
 
 
 if __name__ == '__main__':
