@@ -48,11 +48,15 @@ SPGRAD_EXPORTS = ("imx_detector_loss_grad", "imx_desc_loss_sparse_grad")
 # libimx_otgrad.so (C ABI: include/imx_otgrad.h): the SuperGlue match loss through the unrolled Sinkhorn, value-and-gradient, on libimx.so's handles
 OTGRAD_LIB_PATH = os.path.join(_HERE, "libimx_otgrad.so")
 OTGRAD_EXPORTS = ("imx_ot_match_loss_grad",)
+# libimx_mhagrad.so (C ABI: include/imx_mhagrad.h): the GNN's attention in its training form (forward with the row log-sum-exp, backward), on libimx.so's handles
+MHAGRAD_LIB_PATH = os.path.join(_HERE, "libimx_mhagrad.so")
+MHAGRAD_EXPORTS = ("imx_mha_forward_train", "imx_mha_backward")
 
 _lib = None
 _sptrain = None
 _spgrad = None
 _otgrad = None
+_mhagrad = None
 
 
 def load_library():
@@ -172,4 +176,22 @@ def load_otgrad_library():
     for name in OTGRAD_EXPORTS:
         getattr(lib, name)
     _otgrad = lib
+    return lib
+
+
+def load_mhagrad_library():
+    """Load libimx_mhagrad.so (built beside libimx.so by the same make); libimx.so is loaded first: it makes the handles."""
+    global _mhagrad
+    if _mhagrad is not None:
+        return _mhagrad
+    load_library()
+    if not os.path.exists(MHAGRAD_LIB_PATH):
+        raise RuntimeError(f"libimx_mhagrad.so not found at {MHAGRAD_LIB_PATH}: build it with `make -C image-matching_amd/csrc`")
+    lib = ctypes.CDLL(MHAGRAD_LIB_PATH)
+    vp, i32, f32p = ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p
+    lib.imx_mha_forward_train.argtypes = [vp, i32, i32, i32, i32, i32, f32p, f32p, f32p, vp, vp, f32p, f32p, vp]
+    lib.imx_mha_backward.argtypes = [vp, i32, i32, i32, i32, i32, f32p, f32p, f32p, f32p, f32p, f32p, vp, vp, f32p, f32p, f32p, vp]
+    for name in MHAGRAD_EXPORTS:
+        getattr(lib, name)
+    _mhagrad = lib
     return lib

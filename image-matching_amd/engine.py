@@ -783,6 +783,60 @@ class Engine:
                                                     _ptr(res.get("grad_scores")), _ptr(res.get("grad_bin")), _ptr(res["flag"]), _stream(dev)))
         return res
 
+    # ------------------------------------------------------------------ the GNN's attention, training form (include/imx_mhagrad.h)
+    @property
+    def mhg(self):
+        """libimx_mhagrad.so, loaded on the first use"""
+        if getattr(self, "_mhg", None) is None:
+            self._mhg = L.load_mhagrad_library()
+        return self._mhg
+
+    def _mha_shapes(self, who, q, k, v):
+        """(B, D, H, N, M) of q (B,D,H,N) and k, v (B,D,H,M), the reference's view(B, dim, heads, -1)"""
+        if q.dim() != 4 or k.dim() != 4:
+            raise ImxError(f"{who}: q and k must be (B,D,H,N) and (B,D,H,M), got {tuple(q.shape)} and {tuple(k.shape)}")
+        B, D, H, N = (int(s) for s in q.shape)
+        M = int(k.shape[3])
+        if tuple(k.shape) != (B, D, H, M) or tuple(v.shape) != (B, D, H, M):
+            raise ImxError(f"{who}: k and v must be ({B},{D},{H},M), got {tuple(k.shape)} and {tuple(v.shape)}")
+        return B, D, H, N, M
+
+    def mha_forward_train(self, q, k, v, nq=None, nk=None, want_lse=True):
+        """attention() of superglue/models/superglue_train.py:82-86 in its training form: q (B,D,H,N), k and v (B,D,H,M) fp32 in the
+        reference's own layout, nq / nk (B) int32 counts or None = all.  Returns dict: out (B,D,H,N) = softmax(q^T k / sqrt(D)) v (0 on
+        queries past nq) and, unless want_lse is False, lse (B,H,N), the row log-sum-exp the backward recomputes the probabilities from.
+        No (N, M) matrix is stored.  No host synchronisation."""
+        dev = self.device
+        B, D, H, N, M = self._mha_shapes("mha_forward_train", q, k, v)
+        q, k, v = (self._f32(t, s, f"mha_forward_train: {n}") for t, s, n in ((q, (B, D, H, N), "q"), (k, (B, D, H, M), "k"), (v, (B, D, H, M), "v")))
+        nq, nk = self._counts(nq, B, "mha_forward_train: nq"), self._counts(nk, B, "mha_forward_train: nk")
+        res = {"out": torch.empty(B, D, H, N, dtype=torch.float32, device=dev)}
+        if want_lse:
+            res["lse"] = torch.empty(B, H, N, dtype=torch.float32, device=dev)
+        self._check(self.mhg.imx_mha_forward_train(self.handle, B, H, D, N, M, _ptr(q), _ptr(k), _ptr(v), _ptr(nq), _ptr(nk),
+                                                   _ptr(res["out"]), _ptr(res.get("lse")), _stream(dev)))
+        return res
+
+    def mha_backward(self, q, k, v, out, lse, dout, nq=None, nk=None, want=(True, True, True)):
+        """The backward of mha_forward_train from dout (B,D,H,N), with the forward's q, k, v, out and lse: the probabilities are
+        recomputed tile by tile from lse.  Returns dict with dq (B,D,H,N), dk and dv (B,D,H,M) (0 past the counts), each only where
+        `want` = (dq, dk, dv) asks for it; a gradient's bits do not depend on which others are formed.  No host synchronisation."""
+        dev = self.device
+        B, D, H, N, M = self._mha_shapes("mha_backward", q, k, v)
+        q, k, v = (self._f32(t, s, f"mha_backward: {n}") for t, s, n in ((q, (B, D, H, N), "q"), (k, (B, D, H, M), "k"), (v, (B, D, H, M), "v")))
+        out, dout = self._f32(out, (B, D, H, N), "mha_backward: out"), self._f32(dout, (B, D, H, N), "mha_backward: dout")
+        lse = self._f32(lse, (B, H, N), "mha_backward: lse")
+        nq, nk = self._counts(nq, B, "mha_backward: nq"), self._counts(nk, B, "mha_backward: nk")
+        if len(want) != 3:
+            raise ImxError(f"mha_backward: want must be three flags (dq, dk, dv), got {want!r}")
+        res = {}
+        for name, w, n in (("dq", want[0], N), ("dk", want[1], M), ("dv", want[2], M)):
+            if w:
+                res[name] = torch.empty(B, D, H, n, dtype=torch.float32, device=dev)
+        self._check(self.mhg.imx_mha_backward(self.handle, B, H, D, N, M, _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(dout),
+                                              _ptr(nq), _ptr(nk), _ptr(res.get("dq")), _ptr(res.get("dk")), _ptr(res.get("dv")), _stream(dev)))
+        return res
+
     # ------------------------------------------------------------------ kernel-form options (include/imx.h: imx_set_option)
     def set_option(self, key, value):
         """'mfma' = 'x3' | 'f32', 'latency_forms' = 'auto' | 'off' | 'on' | 'unfused', 'conv' = 'wino' | 'wino_h' | 'wino32' | 'direct',

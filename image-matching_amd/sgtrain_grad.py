@@ -8,6 +8,13 @@ the network.
     loss = match_loss(engine, scores, self.bin_score, all_matches, n_all, iters).mean()
     loss.backward()
 
+The attention of the GNN (superglue_train.py:82-86) is here as well, forward and backward from libimx (include/imx_mhagrad.h): inside the
+reference's MultiHeadedAttention.forward,
+
+    x, _ = attention(engine, query, key, value)
+
+keeps O(B H N) floats per layer for the backward instead of the (B, H, N, M) probabilities.
+
 Inputs are contiguous fp32 cuda tensors; anything else raises (no silent copy, no CPU path)."""
 import torch
 from torch.autograd.function import once_differentiable
@@ -50,3 +57,39 @@ def match_loss(engine, scores, bin_score, all_matches, n_all, iters, n0=None, n1
     """The per-pair loss (B) of superglue_train.py:289-299 on scores (B,N0,N1) = einsum(mdesc0, mdesc1) / sqrt(d), replacing lines
     271-299 of the reference's forward; `.backward()` reaches scores and bin_score."""
     return ot_match_loss.apply(engine, scores, bin_score, all_matches, n_all, int(iters), n0, n1)[0]
+
+
+class mha(torch.autograd.Function):
+    """mha.apply(engine, query, key, value, nq, nk): softmax(query^T key / sqrt(D)) value per (pair, head) on the reference's own
+    (B, D, H, N) / (B, D, H, M) tensors, differentiable with respect to query, key and value.  Saved for the backward: query, key, value,
+    the output and the row log-sum-exp (B, H, N) -- nothing of size N M; the backward recomputes the probabilities (Engine.mha_backward).
+    nq / nk (B) int32 counts of a padded batch or None."""
+
+    @staticmethod
+    def forward(ctx, engine, query, key, value, nq=None, nk=None):
+        for t, what in ((query, "query"), (key, "key"), (value, "value")):
+            _require(t, f"mha: {what}")
+        res = engine.mha_forward_train(query, key, value, nq=nq, nk=nk)
+        ctx.engine, ctx.nq, ctx.nk = engine, nq, nk
+        ctx.save_for_backward(query, key, value, res["out"], res["lse"])
+        return res["out"]
+
+    @staticmethod
+    @once_differentiable                                                 # the kernels form first derivatives only
+    def backward(ctx, grad_out):
+        query, key, value, out, lse = ctx.saved_tensors
+        need = ctx.needs_input_grad[1:4]
+        if not any(need):
+            return (None,) * 6
+        grad_out = grad_out.contiguous()                                 # (autograd's own tensor: the merge's backward may hand over a view)
+        _require(grad_out, "mha: grad_out")
+        g = ctx.engine.mha_backward(query, key, value, out, lse, grad_out, nq=ctx.nq, nk=ctx.nk, want=tuple(need))
+        return None, g.get("dq"), g.get("dk"), g.get("dv"), None, None
+
+
+def attention(engine, query, key, value, nq=None, nk=None):
+    """attention() of superglue_train.py:82-86 with the engine in front: (x, None), x = einsum('bhnm,bdhm->bdhn', softmax(einsum(
+    'bdhn,bdhm->bhnm', query, key) / dim ** .5, dim=-1), value).  The reference returns the probabilities second and discards them at
+    its only call site (`x, _ = attention(...)`); they are never formed here, so None stands for them.  `.backward()` reaches query, key
+    and value through the library's kernels."""
+    return mha.apply(engine, query, key, value, nq, nk), None
