@@ -51,12 +51,16 @@ OTGRAD_EXPORTS = ("imx_ot_match_loss_grad",)
 # libimx_mhagrad.so (C ABI: include/imx_mhagrad.h): the GNN's attention in its training form (forward with the row log-sum-exp, backward), on libimx.so's handles
 MHAGRAD_LIB_PATH = os.path.join(_HERE, "libimx_mhagrad.so")
 MHAGRAD_EXPORTS = ("imx_mha_forward_train", "imx_mha_backward")
+# libimx_lingrad.so (C ABI: include/imx_lingrad.h): the 1x1 convolutions of the GNN in their training form (forward, and the gradients at the inputs, weight and bias), on libimx.so's handles
+LINGRAD_LIB_PATH = os.path.join(_HERE, "libimx_lingrad.so")
+LINGRAD_EXPORTS = ("imx_conv1x1_forward_train", "imx_conv1x1_backward")
 
 _lib = None
 _sptrain = None
 _spgrad = None
 _otgrad = None
 _mhagrad = None
+_lingrad = None
 
 
 def load_library():
@@ -194,4 +198,22 @@ def load_mhagrad_library():
     for name in MHAGRAD_EXPORTS:
         getattr(lib, name)
     _mhagrad = lib
+    return lib
+
+
+def load_lingrad_library():
+    """Load libimx_lingrad.so (built beside libimx.so by the same make); libimx.so is loaded first: it makes the handles."""
+    global _lingrad
+    if _lingrad is not None:
+        return _lingrad
+    load_library()
+    if not os.path.exists(LINGRAD_LIB_PATH):
+        raise RuntimeError(f"libimx_lingrad.so not found at {LINGRAD_LIB_PATH}: build it with `make -C image-matching_amd/csrc`")
+    lib = ctypes.CDLL(LINGRAD_LIB_PATH)
+    vp, i32, f32p = ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p
+    lib.imx_conv1x1_forward_train.argtypes = [vp, i32, i32, i32, i32, i32, f32p, f32p, f32p, f32p, vp, f32p, vp]
+    lib.imx_conv1x1_backward.argtypes = [vp, i32, i32, i32, i32, i32, f32p, f32p, f32p, f32p, vp, f32p, f32p, f32p, f32p, vp]
+    for name in LINGRAD_EXPORTS:
+        getattr(lib, name)
+    _lingrad = lib
     return lib

@@ -837,6 +837,65 @@ class Engine:
                                               _ptr(nq), _ptr(nk), _ptr(res.get("dq")), _ptr(res.get("dk")), _ptr(res.get("dv")), _stream(dev)))
         return res
 
+    # ------------------------------------------------------------------ the 1x1 convolutions, training form (include/imx_lingrad.h)
+    @property
+    def ling(self):
+        """libimx_lingrad.so, loaded on the first use"""
+        if getattr(self, "_ling", None) is None:
+            self._ling = L.load_lingrad_library()
+        return self._ling
+
+    def _conv1x1_args(self, who, x0, w, x1):
+        """(B, Cout, C0, C1, N) of x0 (B,C0,N), x1 (B,C1,N) or None, w (Cout, C0+C1) or the (Cout, C0+C1, 1) parameter itself; every
+        tensor a contiguous fp32 cuda tensor, otherwise ImxError (no silent copy)"""
+        for t, what in ((x0, "x0"), (w, "w")) + (((x1, "x1"),) if x1 is not None else ()):
+            if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ImxError(f"{who}: {what} must be a contiguous fp32 cuda tensor")
+        if x0.dim() != 3 or (x1 is not None and (x1.dim() != 3 or x1.shape[0] != x0.shape[0] or x1.shape[2] != x0.shape[2])):
+            raise ImxError(f"{who}: x0 and x1 must be (B,C0,N) and (B,C1,N), got {tuple(x0.shape)} and {None if x1 is None else tuple(x1.shape)}")
+        B, C0, N = (int(s) for s in x0.shape)
+        C1 = 0 if x1 is None else int(x1.shape[1])
+        if w.dim() not in (2, 3) or int(w.shape[1]) != C0 + C1 or (w.dim() == 3 and int(w.shape[2]) != 1):
+            raise ImxError(f"{who}: w must be (Cout,{C0 + C1}) or (Cout,{C0 + C1},1), got {tuple(w.shape)}")
+        return B, int(w.shape[0]), C0, C1, N
+
+    def conv1x1_forward_train(self, x0, w, bias=None, x1=None, n=None):
+        """F.conv1d(torch.cat([x0, x1], 1), w, bias) of kernel size 1 without forming the concatenation: x0 (B,C0,N), x1 (B,C1,N) or None,
+        w (Cout, C0+C1[, 1]), bias (Cout) or None, n (B) int32 counts or None = all.  Returns dict: y (B,Cout,N), 0 on columns past n.
+        No host synchronisation."""
+        dev = self.device
+        B, Cout, C0, C1, N = self._conv1x1_args("conv1x1_forward_train", x0, w, x1)
+        if bias is not None:
+            bias = self._f32(bias, (Cout,), "conv1x1_forward_train: bias")
+        n = self._counts(n, B, "conv1x1_forward_train: n")
+        res = {"y": torch.empty(B, Cout, N, dtype=torch.float32, device=dev)}
+        self._check(self.ling.imx_conv1x1_forward_train(self.handle, B, Cout, C0, C1, N, _ptr(x0), _ptr(x1), _ptr(w), _ptr(bias), _ptr(n),
+                                                        _ptr(res["y"]), _stream(dev)))
+        return res
+
+    def conv1x1_backward(self, x0, w, dy, x1=None, n=None, want=(True, True, True, True)):
+        """The backward of conv1x1_forward_train from dy (B,Cout,N).  Returns dict with dx0 (B,C0,N), dx1 (B,C1,N) (0 past the counts),
+        dw (the shape of w) and db (Cout) (overwritten, not accumulated), each only where `want` = (dx0, dx1, dw, db) asks for it;
+        want[1] is ignored without x1.  A gradient's bits do not depend on which others are formed.  No host synchronisation."""
+        dev = self.device
+        B, Cout, C0, C1, N = self._conv1x1_args("conv1x1_backward", x0, w, x1)
+        if not isinstance(dy, torch.Tensor) or dy.device.type != "cuda" or dy.dtype != torch.float32 or not dy.is_contiguous():
+            raise ImxError("conv1x1_backward: dy must be a contiguous fp32 cuda tensor")
+        if tuple(dy.shape) != (B, Cout, N):
+            raise ImxError(f"conv1x1_backward: dy must be ({B},{Cout},{N}), got {tuple(dy.shape)}")
+        n = self._counts(n, B, "conv1x1_backward: n")
+        if len(want) != 4:
+            raise ImxError(f"conv1x1_backward: want must be four flags (dx0, dx1, dw, db), got {want!r}")
+        res = {}
+        for name, wanted, shape in (("dx0", want[0], (B, C0, N)), ("dx1", want[1] and x1 is not None, (B, C1, N)),
+                                    ("dw", want[2], tuple(w.shape)), ("db", want[3], (Cout,))):
+            if wanted:
+                res[name] = torch.empty(shape, dtype=torch.float32, device=dev)
+        self._check(self.ling.imx_conv1x1_backward(self.handle, B, Cout, C0, C1, N, _ptr(x0), _ptr(x1), _ptr(w), _ptr(dy), _ptr(n),
+                                                   _ptr(res.get("dx0")), _ptr(res.get("dx1")), _ptr(res.get("dw")), _ptr(res.get("db")),
+                                                   _stream(dev)))
+        return res
+
     # ------------------------------------------------------------------ kernel-form options (include/imx.h: imx_set_option)
     def set_option(self, key, value):
         """'mfma' = 'x3' | 'f32', 'latency_forms' = 'auto' | 'off' | 'on' | 'unfused', 'conv' = 'wino' | 'wino_h' | 'wino32' | 'direct',

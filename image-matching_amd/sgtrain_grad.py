@@ -15,6 +15,15 @@ reference's MultiHeadedAttention.forward,
 
 keeps O(B H N) floats per layer for the backward instead of the (B, H, N, M) probabilities.
 
+The 1x1 convolutions around it (superglue_train.py:52, 96, 97, 111) are here too, forward and backward from libimx
+(include/imx_lingrad.h): inside MultiHeadedAttention.forward and MLP,
+
+    y = conv1d(engine, x, conv.weight, conv.bias)                # nn.Conv1d(kernel_size=1)
+    y = conv1d(engine, x, conv.weight, conv.bias, x1=message)    # the same on torch.cat([x, message], 1), never formed
+
+and a whole layer of the GNN, `delta0 = attentional_propagation(engine, layer, desc0, src0)` for `layer(desc0, src0)` in
+AttentionalGNN.forward: every matrix product in libimx, BatchNorm and ReLU PyTorch's.
+
 Inputs are contiguous fp32 cuda tensors; anything else raises (no silent copy, no CPU path)."""
 import torch
 from torch.autograd.function import once_differentiable
@@ -93,3 +102,55 @@ def attention(engine, query, key, value, nq=None, nk=None):
     its only call site (`x, _ = attention(...)`); they are never formed here, so None stands for them.  `.backward()` reaches query, key
     and value through the library's kernels."""
     return mha.apply(engine, query, key, value, nq, nk), None
+
+
+class conv1x1(torch.autograd.Function):
+    """conv1x1.apply(engine, x, weight, bias, x1, n): F.conv1d(torch.cat([x, x1], 1), weight, bias) of kernel size 1 on x (B,C0,N), x1
+    (B,C1,N) or None, weight (Cout, C0+C1, 1) or (Cout, C0+C1), bias (Cout) or None, differentiable with respect to x, weight, bias and
+    x1.  Saved for the backward: the inputs only (x, x1, weight).  n (B) int32 counts of a padded batch or None."""
+
+    @staticmethod
+    def forward(ctx, engine, x, weight, bias=None, x1=None, n=None):
+        for t, what in ((x, "x"), (weight, "weight")) + (((bias, "bias"),) if bias is not None else ()) + (((x1, "x1"),) if x1 is not None else ()):
+            _require(t, f"conv1x1: {what}")
+        y = engine.conv1x1_forward_train(x, weight, bias, x1=x1, n=n)["y"]
+        ctx.engine, ctx.n, ctx.has_x1 = engine, n, x1 is not None
+        ctx.save_for_backward(x, weight, *((x1,) if x1 is not None else ()))
+        return y
+
+    @staticmethod
+    @once_differentiable                                                 # the kernels form first derivatives only
+    def backward(ctx, grad_y):
+        x, weight = ctx.saved_tensors[:2]
+        x1 = ctx.saved_tensors[2] if ctx.has_x1 else None
+        need = ctx.needs_input_grad                                      # (engine, x, weight, bias, x1, n)
+        want = (need[1], need[4] and ctx.has_x1, need[2], need[3])
+        if not any(want):
+            return (None,) * 6
+        grad_y = grad_y.contiguous()                                     # (autograd's own tensor: it may hand over a view)
+        _require(grad_y, "conv1x1: grad_y")
+        g = ctx.engine.conv1x1_backward(x, weight, grad_y, x1=x1, n=ctx.n, want=want)
+        return None, g.get("dx0"), g.get("dw"), g.get("db"), g.get("dx1"), None
+
+
+def conv1d(engine, x, weight, bias=None, x1=None, n=None):
+    """F.conv1d(torch.cat([x, x1], 1), weight, bias) for a weight of kernel size 1, without forming the cat; x1 = None is
+    F.conv1d(x, weight, bias), what nn.Conv1d(kernel_size=1) computes.  `.backward()` reaches x, x1, weight and bias through the
+    library's kernels.  n (B) int32: columns past n[b] are not read and come out as 0."""
+    return conv1x1.apply(engine, x, weight, bias, x1, n)
+
+
+def attentional_propagation(engine, layer, x, source):
+    """AttentionalPropagation.forward (superglue_train.py:99-116) on any module with .attn.proj, .attn.merge, .attn.dim,
+    .attn.num_heads and .mlp (Conv1d, BatchNorm1d, ReLU, Conv1d): `layer(x, source)` with the six convolutions through conv1d (mlp.0
+    takes x1 = message, so torch.cat([x, message], 1) is never formed) and the attention through attention().  layer.mlp[1]
+    (BatchNorm1d, in whatever mode the module is in; PyTorch updates its running statistics as usual) and layer.mlp[2] are called as
+    they are.  Full frames only, no counts: BatchNorm's batch statistics would count the padding of a ragged batch."""
+    attn, mlp = layer.attn, layer.mlp
+    b = x.size(0)
+    query, key, value = [conv1d(engine, t, l.weight, l.bias).view(b, attn.dim, attn.num_heads, -1)
+                         for l, t in zip(attn.proj, (x, source, source))]
+    m, _ = attention(engine, query, key, value)
+    message = conv1d(engine, m.view(b, attn.dim * attn.num_heads, -1), attn.merge.weight, attn.merge.bias)
+    h = mlp[2](mlp[1](conv1d(engine, x, mlp[0].weight, mlp[0].bias, x1=message)))
+    return conv1d(engine, h.contiguous(), mlp[3].weight, mlp[3].bias)
