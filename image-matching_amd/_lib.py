@@ -54,6 +54,9 @@ MHAGRAD_EXPORTS = ("imx_mha_forward_train", "imx_mha_backward")
 # libimx_lingrad.so (C ABI: include/imx_lingrad.h): the 1x1 convolutions of the GNN in their training form (forward, and the gradients at the inputs, weight and bias), on libimx.so's handles
 LINGRAD_LIB_PATH = os.path.join(_HERE, "libimx_lingrad.so")
 LINGRAD_EXPORTS = ("imx_conv1x1_forward_train", "imx_conv1x1_backward")
+# libimx_bngrad.so (C ABI: include/imx_bngrad.h): BatchNorm1d + ReLU of the MLPs in their training form (forward and backward, one launch each), on libimx.so's handles
+BNGRAD_LIB_PATH = os.path.join(_HERE, "libimx_bngrad.so")
+BNGRAD_EXPORTS = ("imx_bn_relu_forward_train", "imx_bn_relu_backward")
 
 _lib = None
 _sptrain = None
@@ -61,6 +64,7 @@ _spgrad = None
 _otgrad = None
 _mhagrad = None
 _lingrad = None
+_bngrad = None
 
 
 def load_library():
@@ -216,4 +220,22 @@ def load_lingrad_library():
     for name in LINGRAD_EXPORTS:
         getattr(lib, name)
     _lingrad = lib
+    return lib
+
+
+def load_bngrad_library():
+    """Load libimx_bngrad.so (built beside libimx.so by the same make); libimx.so is loaded first: it makes the handles."""
+    global _bngrad
+    if _bngrad is not None:
+        return _bngrad
+    load_library()
+    if not os.path.exists(BNGRAD_LIB_PATH):
+        raise RuntimeError(f"libimx_bngrad.so not found at {BNGRAD_LIB_PATH}: build it with `make -C image-matching_amd/csrc`")
+    lib = ctypes.CDLL(BNGRAD_LIB_PATH)
+    vp, i32, f32, f32p = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_void_p
+    lib.imx_bn_relu_forward_train.argtypes = [vp, i32, i32, i32, i32, f32, f32, f32p, f32p, f32p, vp, f32p, f32p, vp, f32p, f32p, f32p, vp]
+    lib.imx_bn_relu_backward.argtypes = [vp, i32, i32, i32, i32, f32p, f32p, f32p, f32p, f32p, f32p, vp, f32p, f32p, f32p, vp]
+    for name in BNGRAD_EXPORTS:
+        getattr(lib, name)
+    _bngrad = lib
     return lib

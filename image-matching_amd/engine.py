@@ -896,6 +896,71 @@ class Engine:
                                                    _stream(dev)))
         return res
 
+    # ------------------------------------------------------------------ BatchNorm1d + ReLU, training form (include/imx_bngrad.h)
+    @property
+    def bng(self):
+        """libimx_bngrad.so, loaded on the first use"""
+        if getattr(self, "_bng", None) is None:
+            self._bng = L.load_bngrad_library()
+        return self._bng
+
+    def _bn_args(self, who, x, per_channel, full=()):
+        """(B, C, N) of x (B,C,N); per_channel: (tensor or None, name) of shape (C), full: (tensor, name) of x's shape; every tensor a
+        contiguous fp32 cuda tensor, otherwise ImxError (no silent copy)"""
+        for t, what in (((x, "x"),) + tuple(full) + tuple(p for p in per_channel if p[0] is not None)):
+            if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ImxError(f"{who}: {what} must be a contiguous fp32 cuda tensor")
+        if x.dim() != 3:
+            raise ImxError(f"{who}: x must be (B,C,N), got {tuple(x.shape)}")
+        B, C, N = (int(s) for s in x.shape)
+        for t, what in full:
+            if tuple(t.shape) != (B, C, N):
+                raise ImxError(f"{who}: {what} must be ({B},{C},{N}), got {tuple(t.shape)}")
+        for t, what in per_channel:
+            if t is not None and tuple(t.shape) != (C,):
+                raise ImxError(f"{who}: {what} must be ({C},), got {tuple(t.shape)}")
+        return B, C, N
+
+    def bn_relu_forward_train(self, x, gamma, beta, running_mean=None, running_var=None, num_batches_tracked=None, n=None, training=True,
+                              momentum=0.1, eps=1e-5):
+        """F.relu(F.batch_norm(x, running_mean, running_var, gamma, beta, training, momentum, eps)) on x (B,C,N) in one launch; n (B) int32
+        counts or None = all: the statistics are those of the valid columns of all pairs.  In training mode running_mean / running_var (C)
+        and num_batches_tracked (one int64) are updated in place where given; in evaluation mode the running statistics are required.
+        Returns dict: y (B,C,N) (0 past the counts), mean and rstd (C), what bn_relu_backward needs beside x.  No host synchronisation."""
+        dev = self.device
+        B, C, N = self._bn_args("bn_relu_forward_train", x, ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"),
+                                                             (running_var, "running_var")))
+        if num_batches_tracked is not None and (not isinstance(num_batches_tracked, torch.Tensor) or num_batches_tracked.device.type != "cuda"
+                                                or num_batches_tracked.dtype != torch.int64 or num_batches_tracked.numel() != 1):
+            raise ImxError("bn_relu_forward_train: num_batches_tracked must be a cuda int64 tensor of one element")
+        n = self._counts(n, B, "bn_relu_forward_train: n")
+        res = {"y": torch.empty(B, C, N, dtype=torch.float32, device=dev), "mean": torch.empty(C, dtype=torch.float32, device=dev),
+               "rstd": torch.empty(C, dtype=torch.float32, device=dev)}
+        self._check(self.bng.imx_bn_relu_forward_train(self.handle, B, C, N, 1 if training else 0, float(eps), float(momentum), _ptr(x), _ptr(gamma),
+                                                       _ptr(beta), _ptr(n), _ptr(running_mean), _ptr(running_var), _ptr(num_batches_tracked),
+                                                       _ptr(res["y"]), _ptr(res["mean"]), _ptr(res["rstd"]), _stream(dev)))
+        return res
+
+    def bn_relu_backward(self, x, gamma, beta, mean, rstd, dy, n=None, training=True, want=(True, True, True)):
+        """The backward of bn_relu_forward_train from dy (B,C,N), with the forward's x, mean and rstd: the ReLU mask is recomputed, y is not
+        an input.  Returns dict with dx (B,C,N) (0 past the counts), dgamma and dbeta (C) (overwritten, not accumulated), each only where
+        `want` = (dx, dgamma, dbeta) asks for it; a gradient's bits do not depend on which others are formed.  No host synchronisation."""
+        dev = self.device
+        B, C, N = self._bn_args("bn_relu_backward", x, ((gamma, "gamma"), (beta, "beta"), (mean, "mean"), (rstd, "rstd")), ((dy, "dy"),))
+        if mean is None or rstd is None:
+            raise ImxError("bn_relu_backward: mean and rstd are required")
+        n = self._counts(n, B, "bn_relu_backward: n")
+        if len(want) != 3:
+            raise ImxError(f"bn_relu_backward: want must be three flags (dx, dgamma, dbeta), got {want!r}")
+        res = {}
+        for name, wanted, shape in (("dx", want[0], (B, C, N)), ("dgamma", want[1], (C,)), ("dbeta", want[2], (C,))):
+            if wanted:
+                res[name] = torch.empty(shape, dtype=torch.float32, device=dev)
+        self._check(self.bng.imx_bn_relu_backward(self.handle, B, C, N, 1 if training else 0, _ptr(x), _ptr(gamma), _ptr(beta), _ptr(mean),
+                                                  _ptr(rstd), _ptr(dy), _ptr(n), _ptr(res.get("dx")), _ptr(res.get("dgamma")),
+                                                  _ptr(res.get("dbeta")), _stream(dev)))
+        return res
+
     # ------------------------------------------------------------------ kernel-form options (include/imx.h: imx_set_option)
     def set_option(self, key, value):
         """'mfma' = 'x3' | 'f32', 'latency_forms' = 'auto' | 'off' | 'on' | 'unfused', 'conv' = 'wino' | 'wino_h' | 'wino32' | 'direct',

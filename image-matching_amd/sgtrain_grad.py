@@ -24,6 +24,12 @@ The 1x1 convolutions around it (superglue_train.py:52, 96, 97, 111) are here too
 and a whole layer of the GNN, `delta0 = attentional_propagation(engine, layer, desc0, src0)` for `layer(desc0, src0)` in
 AttentionalGNN.forward: every matrix product in libimx, BatchNorm and ReLU PyTorch's.
 
+BatchNorm1d followed by ReLU (superglue_train.py:55-56, inside every MLP) is here as well, one launch forward and one backward
+(include/imx_bngrad.h): `h = batchnorm_relu(engine, bn, h)` for `relu(bn(h))`, `mlp(engine, seq, x)` for a whole Sequential that the
+reference's MLP() built, `keypoint_encoder(engine, kenc, kpts, scores)` for `kenc(kpts, scores)`, and `gnn_layer(engine, layer, desc0,
+src0, n=n0, ns=n1)` for `layer(desc0, src0)` with everything in libimx -- and with per-pair counts, so a padded batch of pairs with
+different keypoint counts goes through a layer: the BatchNorm statistics are those of the valid columns only.
+
 Inputs are contiguous fp32 cuda tensors; anything else raises (no silent copy, no CPU path)."""
 import torch
 from torch.autograd.function import once_differentiable
@@ -154,3 +160,112 @@ def attentional_propagation(engine, layer, x, source):
     message = conv1d(engine, m.view(b, attn.dim * attn.num_heads, -1), attn.merge.weight, attn.merge.bias)
     h = mlp[2](mlp[1](conv1d(engine, x, mlp[0].weight, mlp[0].bias, x1=message)))
     return conv1d(engine, h.contiguous(), mlp[3].weight, mlp[3].bias)
+
+
+class bn_relu(torch.autograd.Function):
+    """bn_relu.apply(engine, x, gamma, beta, running_mean, running_var, num_batches_tracked, n, training, momentum, eps):
+    F.relu(F.batch_norm(x, running_mean, running_var, gamma, beta, training, momentum, eps)) on x (B,C,N), differentiable with respect to
+    x, gamma and beta.  Saved for the backward: x, gamma, beta and the (C) mean and rstd only -- neither the BatchNorm output nor the ReLU
+    output; the backward recomputes the mask.  The running statistics are updated in place in training mode.  n (B) int32 counts of a
+    padded batch or None."""
+
+    @staticmethod
+    def forward(ctx, engine, x, gamma, beta, running_mean=None, running_var=None, num_batches_tracked=None, n=None, training=True,
+                momentum=0.1, eps=1e-5):
+        for t, what in ((x, "x"), (gamma, "gamma"), (beta, "beta")):
+            _require(t, f"bn_relu: {what}")
+        res = engine.bn_relu_forward_train(x, gamma, beta, running_mean, running_var, num_batches_tracked, n=n, training=training,
+                                           momentum=momentum, eps=eps)
+        ctx.engine, ctx.n, ctx.training = engine, n, bool(training)
+        ctx.save_for_backward(x, gamma, beta, res["mean"], res["rstd"])
+        return res["y"]
+
+    @staticmethod
+    @once_differentiable                                                 # the kernel forms first derivatives only
+    def backward(ctx, grad_y):
+        x, gamma, beta, mean, rstd = ctx.saved_tensors
+        want = tuple(ctx.needs_input_grad[1:4])
+        if not any(want):
+            return (None,) * 11
+        grad_y = grad_y.contiguous()                                     # (autograd's own tensor: it may hand over a view)
+        _require(grad_y, "bn_relu: grad_y")
+        g = ctx.engine.bn_relu_backward(x, gamma, beta, mean, rstd, grad_y, n=ctx.n, training=ctx.training, want=want)
+        return (None, g.get("dx"), g.get("dgamma"), g.get("dbeta")) + (None,) * 7
+
+
+def batchnorm_relu(engine, bn, x, n=None):
+    """F.relu(bn(x)) for an nn.BatchNorm1d module bn on x (B,C,N): bn.training, bn.eps and bn.momentum are honoured, and in training mode
+    bn.running_mean, bn.running_var and bn.num_batches_tracked are updated in place, as the module's own forward does.  momentum = None
+    (the cumulative average), affine = False and track_running_stats = False are not built: ImxError.  n (B) int32: columns past n[b]
+    are not read, come out as 0 and do not enter the statistics."""
+    if not isinstance(bn, torch.nn.BatchNorm1d):
+        raise ImxError(f"batchnorm_relu: bn must be an nn.BatchNorm1d, got {type(bn).__name__}")
+    if bn.momentum is None or not bn.affine or not bn.track_running_stats:
+        raise ImxError("batchnorm_relu: momentum=None, affine=False and track_running_stats=False are not supported")
+    return bn_relu.apply(engine, x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, n, bn.training,
+                         float(bn.momentum), float(bn.eps))
+
+
+def _is_conv1(m):
+    return isinstance(m, torch.nn.Conv1d) and m.kernel_size == (1,) and m.stride == (1,) and m.padding == (0,) and m.groups == 1
+
+
+class _bias_before_batchnorm(torch.autograd.Function):
+    """_bias_before_batchnorm.apply(h, bias) -> h, for h = conv1d(..., bias.detach(), ...) that feeds a BatchNorm1d in training mode.
+    Such a bias has a gradient of exactly 0: it shifts every valid column of its channel alike, the batch mean takes the shift out
+    again, and the gradient is sum_n dx[c,n] over the BatchNorm's input gradient, whose terms cancel identically (sum xhat = 0 and
+    dbeta / M is the mean of g; with counts the sums run over the valid columns, and with M <= 1 dx is 0).  Forming that sum in fp32
+    returns the rounding residue of terms that can be hundreds; this returns the 0 itself and no kernel runs for it."""
+
+    @staticmethod
+    def forward(ctx, h, bias):
+        ctx.like = bias
+        return h.view_as(h)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_h):
+        return grad_h, torch.zeros_like(ctx.like) if ctx.needs_input_grad[1] else None
+
+
+def mlp(engine, seq, x, x1=None, n=None):
+    """seq(torch.cat([x, x1], 1)) for any nn.Sequential that the reference's MLP() builds (superglue_train.py:46-57: Conv1d [BatchNorm1d
+    ReLU] ... Conv1d, kernel size 1): the convolutions through conv1d (the first takes x1, so the cat is never formed), every BatchNorm1d
+    + ReLU through batchnorm_relu.  The bias of a convolution whose BatchNorm is in training mode gets its exact gradient, 0
+    (_bias_before_batchnorm); in evaluation mode it is formed like any other.  Any other layout raises ImxError.  n (B) int32 counts of
+    a padded batch or None."""
+    mods = list(seq)
+    if len(mods) % 3 != 1 or not all(_is_conv1(m) for m in mods[0::3]) or not all(isinstance(m, torch.nn.BatchNorm1d) for m in mods[1::3]) \
+            or not all(isinstance(m, torch.nn.ReLU) for m in mods[2::3]):
+        raise ImxError("mlp: expected Conv1d(kernel_size=1) [BatchNorm1d ReLU Conv1d(kernel_size=1)] ..., got "
+                       + " ".join(type(m).__name__ for m in mods))
+    h = x
+    for i in range(0, len(mods), 3):
+        conv, bias = mods[i], mods[i].bias
+        cancels = bias is not None and i + 1 < len(mods) and mods[i + 1].training
+        h = conv1d(engine, h, conv.weight, bias.detach() if cancels else bias, x1=x1 if i == 0 else None, n=n)
+        if cancels:
+            h = _bias_before_batchnorm.apply(h, bias)
+        if i + 1 < len(mods):
+            h = batchnorm_relu(engine, mods[i + 1], h, n=n)
+    return h
+
+
+def keypoint_encoder(engine, kenc, kpts, scores, n=None):
+    """KeypointEncoder.forward (superglue_train.py:77-79) on kpts (B,N,2) and scores (B,N): kenc.encoder through mlp(), the cat of the
+    transposed keypoints and the scores formed by conv1d's second source."""
+    return mlp(engine, kenc.encoder, kpts.transpose(1, 2).contiguous(), x1=scores.unsqueeze(1).contiguous(), n=n)
+
+
+def gnn_layer(engine, layer, x, source, n=None, ns=None):
+    """AttentionalPropagation.forward (superglue_train.py:114-116) with everything in libimx: the six convolutions through conv1d, the
+    attention through attention(), BatchNorm1d + ReLU through batchnorm_relu (the module's mode, momentum and eps; its buffers are updated
+    in place).  n / ns (B) int32 counts of x's and source's columns in a padded batch, or None: they reach the convolutions, the attention
+    (nq = n, nk = ns) and the BatchNorm, whose statistics are those of the valid columns of all pairs."""
+    attn = layer.attn
+    b = x.size(0)
+    query, key, value = [conv1d(engine, t, l.weight, l.bias, n=c).view(b, attn.dim, attn.num_heads, -1)
+                         for l, t, c in zip(attn.proj, (x, source, source), (n, ns, ns))]
+    m, _ = attention(engine, query, key, value, nq=n, nk=ns)
+    message = conv1d(engine, m.view(b, attn.dim * attn.num_heads, -1), attn.merge.weight, attn.merge.bias, n=n)
+    return mlp(engine, layer.mlp, x, x1=message, n=n)
