@@ -269,8 +269,20 @@ class Engine:
         desc{0,1}: (B,d,N) tensors, any strides.  Returns matches (B,N0) int64 (-1 = rejected), dist1, dist2 (B,N0)."""
         dev = self.device
         desc0, desc1 = desc0.to(dev, torch.float32), desc1.to(dev, torch.float32)
+        # the library reads descriptor_dim channels of B pairs from both sides and B counts through raw pointers: refuse anything
+        # else here instead of reading past a tensor
+        if desc0.dim() != 3 or desc1.dim() != 3:
+            raise ImxError(f"knn_ratio_match: descriptors must be (B,d,N), got {tuple(desc0.shape)} and {tuple(desc1.shape)}")
+        if desc0.shape[1] != self.d or desc1.shape[1] != self.d:
+            raise ImxError(f"knn_ratio_match: descriptor dims {desc0.shape[1]} / {desc1.shape[1]} != configured descriptor_dim {self.d}")
+        if desc0.shape[0] != desc1.shape[0]:
+            raise ImxError(f"knn_ratio_match: the two sides differ in batch size ({desc0.shape[0]} and {desc1.shape[0]})")
         B, _, N0 = desc0.shape
         N1 = desc1.shape[2]
+        for n in (n0, n1):
+            if n is not None and not (isinstance(n, torch.Tensor) and n.dtype == torch.int32 and n.dim() == 1 and n.numel() == B
+                                      and n.device == dev and n.is_contiguous()):
+                raise ImxError(f"knn_ratio_match: counts must be contiguous int32 tensors of {B} elements on {dev}")
         m = torch.empty(B, N0, dtype=torch.int64, device=dev)
         d1 = torch.empty(B, N0, dtype=torch.float32, device=dev)
         d2 = torch.empty(B, N0, dtype=torch.float32, device=dev)
