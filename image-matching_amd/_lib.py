@@ -1,4 +1,4 @@
-"""ctypes binding of libimx.so (C ABI: include/imx.h).  There is no CPU fallback: if the
+"""ctypes binding of libimx.so (C ABI: include/imx.h) and libimx_train.so (include/imx_train.h).  There is no CPU fallback: if the
 library is missing or no GPU is present the product path raises."""
 import ctypes
 import os
@@ -39,32 +39,33 @@ class ImxConfig(ctypes.Structure):
     ]
 
 
-# libimx_sptrain.so (C ABI: include/imx_sptrain.h): the descriptor-training stages, on libimx.so's handles
-SPTRAIN_LIB_PATH = os.path.join(_HERE, "libimx_sptrain.so")
-SPTRAIN_EXPORTS = ("imx_warp_labels", "imx_erode_mask", "imx_detector_loss", "imx_desc_pairs", "imx_desc_loss_sparse")
-# libimx_spgrad.so (C ABI: include/imx_spgrad.h): the two training losses as value-and-gradient calls, on libimx.so's handles
-SPGRAD_LIB_PATH = os.path.join(_HERE, "libimx_spgrad.so")
-SPGRAD_EXPORTS = ("imx_detector_loss_grad", "imx_desc_loss_sparse_grad")
-# libimx_otgrad.so (C ABI: include/imx_otgrad.h): the SuperGlue match loss through the unrolled Sinkhorn, value-and-gradient, on libimx.so's handles
-OTGRAD_LIB_PATH = os.path.join(_HERE, "libimx_otgrad.so")
-OTGRAD_EXPORTS = ("imx_ot_match_loss_grad",)
-# libimx_mhagrad.so (C ABI: include/imx_mhagrad.h): the GNN's attention in its training form (forward with the row log-sum-exp, backward), on libimx.so's handles
-MHAGRAD_LIB_PATH = os.path.join(_HERE, "libimx_mhagrad.so")
-MHAGRAD_EXPORTS = ("imx_mha_forward_train", "imx_mha_backward")
-# libimx_lingrad.so (C ABI: include/imx_lingrad.h): the 1x1 convolutions of the GNN in their training form (forward, and the gradients at the inputs, weight and bias), on libimx.so's handles
-LINGRAD_LIB_PATH = os.path.join(_HERE, "libimx_lingrad.so")
-LINGRAD_EXPORTS = ("imx_conv1x1_forward_train", "imx_conv1x1_backward")
-# libimx_bngrad.so (C ABI: include/imx_bngrad.h): BatchNorm1d + ReLU of the MLPs in their training form (forward and backward, one launch each), on libimx.so's handles
-BNGRAD_LIB_PATH = os.path.join(_HERE, "libimx_bngrad.so")
-BNGRAD_EXPORTS = ("imx_bn_relu_forward_train", "imx_bn_relu_backward")
+# libimx_train.so (C ABI: include/imx_train.h): the training stages, on libimx.so's handles -- name -> argtypes, one line per entry point
+TRAIN_LIB_PATH = os.path.join(_HERE, "libimx_train.so")
+_vp, _i32, _f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+_TRAIN_ARGTYPES = {
+    # SuperPoint descriptor training: labels, masks, the forward values of the two losses
+    "imx_warp_labels": [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp],
+    "imx_erode_mask": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
+    "imx_detector_loss": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp],
+    "imx_desc_pairs": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
+    "imx_desc_loss_sparse": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp],
+    # the two losses as value-and-gradient calls
+    "imx_detector_loss_grad": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
+    "imx_desc_loss_sparse_grad": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    # the SuperGlue match loss through the unrolled Sinkhorn, value-and-gradient
+    "imx_ot_match_loss_grad": [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
+    # the GNN's attention, 1x1 convolutions and BatchNorm1d + ReLU in their training form, forward and backward
+    "imx_mha_forward_train": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "imx_mha_backward": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "imx_conv1x1_forward_train": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "imx_conv1x1_backward": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "imx_bn_relu_forward_train": [_vp, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "imx_bn_relu_backward": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+}
+TRAIN_EXPORTS = tuple(_TRAIN_ARGTYPES)
 
 _lib = None
-_sptrain = None
-_spgrad = None
-_otgrad = None
-_mhagrad = None
-_lingrad = None
-_bngrad = None
+_train = None
 
 
 def load_library():
@@ -129,113 +130,16 @@ def load_library():
     return lib
 
 
-def load_sptrain_library():
-    """Load libimx_sptrain.so (built beside libimx.so by the same make); libimx.so is loaded first: it makes the handles."""
-    global _sptrain
-    if _sptrain is not None:
-        return _sptrain
+def load_train_library():
+    """Load libimx_train.so (built beside libimx.so by the same make); libimx.so is loaded first: it makes the handles."""
+    global _train
+    if _train is not None:
+        return _train
     load_library()
-    if not os.path.exists(SPTRAIN_LIB_PATH):
-        raise RuntimeError(f"libimx_sptrain.so not found at {SPTRAIN_LIB_PATH}: build it with `make -C image-matching_amd/csrc`")
-    lib = ctypes.CDLL(SPTRAIN_LIB_PATH)
-    vp, i32, f32p = ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p
-    lib.imx_warp_labels.argtypes = [vp, f32p, vp, i32, i32, f32p, i32, i32, f32p, f32p, vp, vp]
-    lib.imx_erode_mask.argtypes = [vp, f32p, f32p, i32, i32, i32, i32, vp]
-    lib.imx_detector_loss.argtypes = [vp, f32p, f32p, f32p, i32, i32, i32, f32p, vp]
-    lib.imx_desc_loss_sparse.argtypes = [vp, f32p, f32p, i32, i32, i32, i32, f32p, vp, vp, i32, i32, ctypes.c_float, ctypes.c_float, i32,
-                                         f32p, f32p, vp, vp, vp]
-    lib.imx_desc_pairs.argtypes = [vp, f32p, i32, i32, i32, vp, vp, vp]
-    for name in SPTRAIN_EXPORTS:
-        getattr(lib, name)
-    _sptrain = lib
-    return lib
-
-
-def load_spgrad_library():
-    """Load libimx_spgrad.so (built beside libimx.so by the same make); libimx.so is loaded first: it makes the handles."""
-    global _spgrad
-    if _spgrad is not None:
-        return _spgrad
-    load_library()
-    if not os.path.exists(SPGRAD_LIB_PATH):
-        raise RuntimeError(f"libimx_spgrad.so not found at {SPGRAD_LIB_PATH}: build it with `make -C image-matching_amd/csrc`")
-    lib = ctypes.CDLL(SPGRAD_LIB_PATH)
-    vp, i32, f32p = ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p
-    lib.imx_detector_loss_grad.argtypes = [vp, f32p, f32p, f32p, i32, i32, i32, f32p, f32p, f32p, vp]
-    lib.imx_desc_loss_sparse_grad.argtypes = [vp, f32p, f32p, i32, i32, i32, i32, f32p, vp, vp, i32, i32, ctypes.c_float, ctypes.c_float, i32,
-                                              f32p, f32p, f32p, vp, vp, f32p, f32p, vp]
-    for name in SPGRAD_EXPORTS:
-        getattr(lib, name)
-    _spgrad = lib
-    return lib
-
-
-def load_otgrad_library():
-    """Load libimx_otgrad.so (built beside libimx.so by the same make); libimx.so is loaded first: it makes the handles."""
-    global _otgrad
-    if _otgrad is not None:
-        return _otgrad
-    load_library()
-    if not os.path.exists(OTGRAD_LIB_PATH):
-        raise RuntimeError(f"libimx_otgrad.so not found at {OTGRAD_LIB_PATH}: build it with `make -C image-matching_amd/csrc`")
-    lib = ctypes.CDLL(OTGRAD_LIB_PATH)
-    vp, i32, f32p = ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p
-    lib.imx_ot_match_loss_grad.argtypes = [vp, i32, f32p, i32, i32, vp, vp, f32p, i32, vp, vp, i32, f32p, f32p, f32p, f32p, vp, vp]
-    for name in OTGRAD_EXPORTS:
-        getattr(lib, name)
-    _otgrad = lib
-    return lib
-
-
-def load_mhagrad_library():
-    """Load libimx_mhagrad.so (built beside libimx.so by the same make); libimx.so is loaded first: it makes the handles."""
-    global _mhagrad
-    if _mhagrad is not None:
-        return _mhagrad
-    load_library()
-    if not os.path.exists(MHAGRAD_LIB_PATH):
-        raise RuntimeError(f"libimx_mhagrad.so not found at {MHAGRAD_LIB_PATH}: build it with `make -C image-matching_amd/csrc`")
-    lib = ctypes.CDLL(MHAGRAD_LIB_PATH)
-    vp, i32, f32p = ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p
-    lib.imx_mha_forward_train.argtypes = [vp, i32, i32, i32, i32, i32, f32p, f32p, f32p, vp, vp, f32p, f32p, vp]
-    lib.imx_mha_backward.argtypes = [vp, i32, i32, i32, i32, i32, f32p, f32p, f32p, f32p, f32p, f32p, vp, vp, f32p, f32p, f32p, vp]
-    for name in MHAGRAD_EXPORTS:
-        getattr(lib, name)
-    _mhagrad = lib
-    return lib
-
-
-def load_lingrad_library():
-    """Load libimx_lingrad.so (built beside libimx.so by the same make); libimx.so is loaded first: it makes the handles."""
-    global _lingrad
-    if _lingrad is not None:
-        return _lingrad
-    load_library()
-    if not os.path.exists(LINGRAD_LIB_PATH):
-        raise RuntimeError(f"libimx_lingrad.so not found at {LINGRAD_LIB_PATH}: build it with `make -C image-matching_amd/csrc`")
-    lib = ctypes.CDLL(LINGRAD_LIB_PATH)
-    vp, i32, f32p = ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p
-    lib.imx_conv1x1_forward_train.argtypes = [vp, i32, i32, i32, i32, i32, f32p, f32p, f32p, f32p, vp, f32p, vp]
-    lib.imx_conv1x1_backward.argtypes = [vp, i32, i32, i32, i32, i32, f32p, f32p, f32p, f32p, vp, f32p, f32p, f32p, f32p, vp]
-    for name in LINGRAD_EXPORTS:
-        getattr(lib, name)
-    _lingrad = lib
-    return lib
-
-
-def load_bngrad_library():
-    """Load libimx_bngrad.so (built beside libimx.so by the same make); libimx.so is loaded first: it makes the handles."""
-    global _bngrad
-    if _bngrad is not None:
-        return _bngrad
-    load_library()
-    if not os.path.exists(BNGRAD_LIB_PATH):
-        raise RuntimeError(f"libimx_bngrad.so not found at {BNGRAD_LIB_PATH}: build it with `make -C image-matching_amd/csrc`")
-    lib = ctypes.CDLL(BNGRAD_LIB_PATH)
-    vp, i32, f32, f32p = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_void_p
-    lib.imx_bn_relu_forward_train.argtypes = [vp, i32, i32, i32, i32, f32, f32, f32p, f32p, f32p, vp, f32p, f32p, vp, f32p, f32p, f32p, vp]
-    lib.imx_bn_relu_backward.argtypes = [vp, i32, i32, i32, i32, f32p, f32p, f32p, f32p, f32p, f32p, vp, f32p, f32p, f32p, vp]
-    for name in BNGRAD_EXPORTS:
-        getattr(lib, name)
-    _bngrad = lib
+    if not os.path.exists(TRAIN_LIB_PATH):
+        raise RuntimeError(f"libimx_train.so not found at {TRAIN_LIB_PATH}: build it with `make -C image-matching_amd/csrc`")
+    lib = ctypes.CDLL(TRAIN_LIB_PATH)
+    for name, argtypes in _TRAIN_ARGTYPES.items():
+        getattr(lib, name).argtypes = argtypes          # raises AttributeError if a declared symbol is missing
+    _train = lib
     return lib

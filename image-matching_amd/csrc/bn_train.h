@@ -1,4 +1,4 @@
-// bn_train.h -- launchers of bn_train.hip, the kernels of libimx_bngrad.so (include/imx_bngrad.h): nn.BatchNorm1d followed by nn.ReLU in
+// bn_train.h -- launchers of bn_train.hip, kernels of libimx_train.so (include/imx_train.h): nn.BatchNorm1d followed by nn.ReLU in
 // their training form, forward and backward, one launch each.  DESIGN.md section 16 has the formulas, the launch structure and the
 // summation orders.
 #pragma once

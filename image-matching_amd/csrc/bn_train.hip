@@ -1,4 +1,4 @@
-// bn_train.hip -- nn.BatchNorm1d followed by nn.ReLU in their training form (include/imx_bngrad.h), one launch
+// bn_train.hip -- nn.BatchNorm1d followed by nn.ReLU in their training form (include/imx_train.h), one launch
 // forward and one backward, no workspace.  One workgroup of 256 threads per channel c; with n[b] the pair's count and M their sum:
 //
 //   bn_relu_fwd   mean = sum x / M,  var = sum (x - mean)^2 / M,  rstd = 1 / sqrt(var + eps)       (training; evaluation: the running ones)
@@ -20,6 +20,7 @@
 // off in this file: every fused multiply-add is written as one, which is what makes the mask of the backward equal y > 0 bit for bit.
 // Loads are single dwords (a row of N floats is not 16-byte aligned when N % 4 != 0) and predicated: nothing past a count is ever loaded.
 #include "bn_train.h"
+#include "train_dev.h"
 
 #pragma clang fp contract(off)
 
@@ -51,12 +52,6 @@ __device__ __forceinline__ void channel_counts(const BnArgs& a, int t, unsigned 
   __syncthreads();
   M = (long long)*sM;
   first = *sFirst;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
 }
 
 // the workgroup's sum of u, on every thread; red: four floats of LDS that nothing else uses before the next barrier

@@ -9,10 +9,6 @@
 #include <atomic>
 #include <memory>
 
-namespace imx {
-thread_local const char* last_form = nullptr;
-}
-
 namespace {
 bool ends_with(const std::string& s, const std::string& suf) {
   return s.size() >= suf.size() && s.compare(s.size() - suf.size(), suf.size(), suf) == 0;

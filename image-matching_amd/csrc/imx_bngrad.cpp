@@ -1,13 +1,8 @@
-// imx_bngrad.cpp -- the host unit of libimx_bngrad.so (include/imx_bngrad.h), on the handle libimx.so made: nn.BatchNorm1d followed by
+// imx_bngrad.cpp -- a host unit of libimx_train.so (include/imx_train.h), on the handle libimx.so made: nn.BatchNorm1d followed by
 // nn.ReLU in their training form, forward and backward.  The kernels are bn_train.hip's, one launch per call; no workspace is drawn.
 #include "imx_host.h"
 #include "bn_train.h"
-#include "../../include/imx_bngrad.h"
-
-// libimx_bngrad.so is a library of its own: run() resets the form through this copy, and the calls here report theirs through it
-namespace imx {
-thread_local const char* last_form = nullptr;
-}
+#include "../../include/imx_train.h"
 
 namespace {
 

@@ -43,8 +43,9 @@ struct Options {
 
 // The form a launcher picked ("gemm_x3:bf16x3", "conv3x3_wino24:f32", ...: kernel family, then the matrix pipe it runs on or
 // "hbm" for streaming kernels).  Set by every launch_* that has more than one form, read by imx_host.h's per-launch timing (run) so
-// that imx_timing_form reports what actually ran.
-extern thread_local const char* last_form;
+// that imx_timing_form reports what actually ran.  One hidden instance per library (libimx.so, libimx_train.so): run() and the launchers it
+// calls are always of the same library.
+inline thread_local const char* last_form = nullptr;
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE attribute of a kernel: `done_mask` (one static per kernel
 // instantiation at the call site) remembers the devices it has been raised on, so a process holding handles on two devices

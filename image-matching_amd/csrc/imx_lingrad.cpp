@@ -1,15 +1,10 @@
-// imx_lingrad.cpp -- the host unit of libimx_lingrad.so (include/imx_lingrad.h), on the handle libimx.so made: nn.Conv1d(kernel_size=1)
+// imx_lingrad.cpp -- a host unit of libimx_train.so (include/imx_train.h), on the handle libimx.so made: nn.Conv1d(kernel_size=1)
 // on torch.cat([x0, x1], 1) in its training form, forward and the gradients at the inputs, the weight and the bias.  The kernels are
 // lin_train.hip's; gemm*.hip, gnn_tail.hip and the inference path are not linked here and not touched.  The one scratch buffer
 // ("lin.part", B ceil(N / 256) Cout (C0 + C1 + 1) floats) is written by the backward call that reads it.
 #include "imx_host.h"
 #include "lin_train.h"
-#include "../../include/imx_lingrad.h"
-
-// libimx_lingrad.so is a library of its own: run() resets the form through this copy (the kernels here have one form each)
-namespace imx {
-thread_local const char* last_form = nullptr;
-}
+#include "../../include/imx_train.h"
 
 namespace {
 

@@ -1,17 +1,12 @@
-// imx_mhagrad.cpp -- the host unit of libimx_mhagrad.so (include/imx_mhagrad.h), on the handle libimx.so made: the attention of
+// imx_mhagrad.cpp -- a host unit of libimx_train.so (include/imx_train.h), on the handle libimx.so made: the attention of
 // SuperGlue's GNN in its training form, a forward that keeps the row log-sum-exp and the backward from it.  The kernels are
 // mha_train.hip's; attention.hip and the inference path are not linked here and not touched.  The one scratch buffer ("mha.delta",
 // B H N floats) is written in full by the backward call that reads it.
 #include "imx_host.h"
 #include "mha_train.h"
-#include "../../include/imx_mhagrad.h"
+#include "../../include/imx_train.h"
 
 #include <cmath>
-
-// libimx_mhagrad.so is a library of its own: run() resets the form through this copy (the kernels here have one form each)
-namespace imx {
-thread_local const char* last_form = nullptr;
-}
 
 namespace {
 

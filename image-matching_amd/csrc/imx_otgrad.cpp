@@ -1,15 +1,10 @@
-// imx_otgrad.cpp -- the host unit of libimx_otgrad.so (include/imx_otgrad.h), on the handle libimx.so made: the SuperGlue match loss
+// imx_otgrad.cpp -- a host unit of libimx_train.so (include/imx_train.h), on the handle libimx.so made: the SuperGlue match loss
 // through the unrolled Sinkhorn as one value-and-gradient call.  The kernels are otgrad.hip's; the forward's Sinkhorn and match kernels
 // (sg_misc.hip, trainpairs.hip) are not linked here and not touched.  Every scratch buffer ("otg.*") is written, as far as it is
 // read, by the call that reads it: 2 (iters + 1) (N0 + N1 + 2) floats per pair and a few vectors, nothing of matrix size.
 #include "imx_host.h"
 #include "otgrad.h"
-#include "../../include/imx_otgrad.h"
-
-// libimx_otgrad.so is a library of its own: run() resets the form through this copy (the kernels here have one form each)
-namespace imx {
-thread_local const char* last_form = nullptr;
-}
+#include "../../include/imx_train.h"
 
 extern "C" {
 

@@ -1,14 +1,9 @@
-// imx_spgrad.cpp -- the host unit of libimx_spgrad.so (include/imx_spgrad.h), on the handle libimx.so made: the two SuperPoint training
+// imx_spgrad.cpp -- a host unit of libimx_train.so (include/imx_train.h), on the handle libimx.so made: the two SuperPoint training
 // losses as value-and-gradient calls, imx_detector_loss_grad and imx_desc_loss_sparse_grad.  The values come from the forward's own
-// launchers (sptrain.hip is linked into this library too: one definition of the device code), the gradients from spgrad.hip.  Every
+// launchers (sptrain.hip, linked once into the library: one definition of the device code), the gradients from spgrad.hip.  Every
 // scratch buffer ("spg.*") is written in full, or as far as it is read, by the call that reads it.
 #include "imx_host.h"
-#include "../../include/imx_spgrad.h"
-
-// libimx_spgrad.so is a library of its own (include/imx_spgrad.h): its launchers report their form through this copy
-namespace imx {
-thread_local const char* last_form = nullptr;
-}
+#include "../../include/imx_train.h"
 
 namespace {
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }

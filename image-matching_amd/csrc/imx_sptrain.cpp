@@ -1,13 +1,8 @@
-// imx_sptrain.cpp -- the host unit of libimx_sptrain.so (include/imx_sptrain.h), on the handle libimx.so made: SuperPoint descriptor training up to the forward value of the objective (superpoint_train_descriptor.py ->
+// imx_sptrain.cpp -- a host unit of libimx_train.so (include/imx_train.h), on the handle libimx.so made: SuperPoint descriptor training up to the forward value of the objective (superpoint_train_descriptor.py ->
 // datasets/ALLSS.py -> superpoint/Train_model_heatmap.py:83-314): the entry points imx_warp_labels, imx_erode_mask,
 // imx_detector_loss, imx_desc_pairs and imx_desc_loss_sparse.  Every scratch buffer ("spt.*") is written in full by the call that reads it.
 #include "imx_host.h"
-#include "../../include/imx_sptrain.h"
-
-// libimx_sptrain.so is a library of its own (include/imx_sptrain.h): its launchers report their form through this copy
-namespace imx {
-thread_local const char* last_form = nullptr;
-}
+#include "../../include/imx_train.h"
 
 namespace {
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }

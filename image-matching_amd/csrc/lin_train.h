@@ -1,4 +1,4 @@
-// lin_train.h -- launchers of lin_train.hip, the kernels of libimx_lingrad.so (include/imx_lingrad.h): nn.Conv1d(kernel_size=1) on
+// lin_train.h -- launchers of lin_train.hip, kernels of libimx_train.so (include/imx_train.h): nn.Conv1d(kernel_size=1) on
 // torch.cat([x0, x1], 1) in its training form, forward and the three gradients.  DESIGN.md section 15 has the formulas, the launch
 // structure and the summation orders.
 #pragma once

@@ -1,5 +1,5 @@
 // lin_train.hip -- nn.Conv1d(kernel_size=1) on torch.cat([x0, x1], 1) in its training form on the fp32 matrix cores
-// (include/imx_lingrad.h).  Per pair b, with xcat the concatenation of x0 and x1 over channels, Cin = C0 + C1:
+// (include/imx_train.h).  Per pair b, with xcat the concatenation of x0 and x1 over channels, Cin = C0 + C1:
 //
 //   lin_fwd         y[o][n]  = bias[o] + sum_c w[o][c] xcat[c][n]          workgroup: 64 output channels x 64 columns
 //   lin_dx          dx[c][n] = sum_o w[o][c] dy[o][n]                      workgroup: 64 input channels x 64 columns
@@ -23,10 +23,9 @@
 // the pair's count skipped; lin_dw_reduce adds a pair's slabs ascending from +0 (slabs past the count skipped), then the pairs ascending
 // from +0 (pairs of count 0 skipped).  No floating-point atomics, no workgroup waits on another.
 #include "lin_train.h"
+#include "train_dev.h"
 
 namespace imx {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
@@ -34,13 +33,6 @@ constexpr int TS = 33;                       // row stride of an LDS tile image 
 constexpr int kThreads = 256;                // 4 waves, 2 x 2 sub-tiles of 32 x 32
 constexpr int kTileRegs = kLinTile * 32 / kThreads;   // floats per thread of one [64][32] tile
 
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : v > hi ? hi : v; }
-__device__ __forceinline__ int crow(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
-__device__ __forceinline__ f32x16 zero16() {
-  const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  return z;
-}
-__device__ __forceinline__ f32x16 mma(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
 // a chunk closes its block of 128 when it is the block's fourth or the last of all
 __device__ __forceinline__ bool closes_block(int chunk, int nchunks) { return (chunk & 3) == 3 || chunk == nchunks - 1; }
 
@@ -245,8 +237,6 @@ __global__ __launch_bounds__(kThreads) void lin_dw_reduce_kernel(LinArgs a, int 
   if (c < Cin) a.dw[(size_t)o * Cin + c] = total;
   else a.db[o] = total;
 }
-
-inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 }  // namespace
 

@@ -1,4 +1,4 @@
-// mha_train.h -- launchers of mha_train.hip, the kernels of libimx_mhagrad.so (include/imx_mhagrad.h): the attention of SuperGlue's GNN in
+// mha_train.h -- launchers of mha_train.hip, kernels of libimx_train.so (include/imx_train.h): the attention of SuperGlue's GNN in
 // its training form, a forward that keeps the row log-sum-exp and the backward that recomputes the probabilities from it.  DESIGN.md
 // section 14 has the formulas, the launch structure and the summation orders.
 #pragma once

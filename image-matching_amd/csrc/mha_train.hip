@@ -1,5 +1,5 @@
 // mha_train.hip -- the attention of SuperGlue's GNN (superglue/models/superglue_train.py:82-86: einsum, softmax, einsum) in its training
-// form, flash style on the fp32 matrix cores (include/imx_mhagrad.h).  Per (pair b, head h), scale = 1 / sqrt(D):
+// form, flash style on the fp32 matrix cores (include/imx_train.h).  Per (pair b, head h), scale = 1 / sqrt(D):
 //
 //   forward    S = scale Q^T K,  P = softmax_rows(S),  O = P V,  lse_i = log sum_j exp(S_ij)                      (one launch)
 //   backward   delta_i = sum_c dO_ic O_ic                                                                       (one small launch)
@@ -30,12 +30,11 @@
 // Ragged batches: queries past nq[b] and keys past nk[b] are never loaded (they are staged as zeros and their probabilities are selected
 // to zero, so NaN there cannot leak); every output is written in full, with 0 there.
 #include "mha_train.h"
+#include "train_dev.h"
 
 #include <math.h>
 
 namespace imx {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
@@ -43,13 +42,6 @@ constexpr int TS = 33;                       // row stride of an LDS tile image 
 constexpr int kWaves = 4, kBlock = 32 * kWaves;   // keypoints per workgroup on the side that owns the accumulators
 constexpr float kLog2e = 1.4426950408889634f;
 
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : v > hi ? hi : v; }
-__device__ __forceinline__ int crow(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
-__device__ __forceinline__ f32x16 zero16() {
-  const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  return z;
-}
-__device__ __forceinline__ f32x16 mma(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ float xhalf_max(float x) { return fmaxf(x, __shfl_xor(x, 32)); }
 __device__ __forceinline__ float xhalf_sum(float x) { return x + __shfl_xor(x, 32); }
 
@@ -339,8 +331,6 @@ __global__ __launch_bounds__(64 * kWaves) void mha_dkdv_kernel(MhaArgs a) {
   if (want_k) store_acc<D, CB>(a.dk + koff, csk, ki, a.M, kv, GK, 1.f, hi);
   if (want_v) store_acc<D, CB>(a.dv + koff, csk, ki, a.M, kv, GV, 1.f, hi);
 }
-
-inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 }  // namespace
 

@@ -1,4 +1,4 @@
-// otgrad.h -- launchers of otgrad.hip, the kernels of libimx_otgrad.so (include/imx_otgrad.h): the SuperGlue match loss through the
+// otgrad.h -- launchers of otgrad.hip, kernels of libimx_train.so (include/imx_train.h): the SuperGlue match loss through the
 // unrolled log-domain Sinkhorn as a value-and-gradient call.  DESIGN.md section 13 has the derivative rules and the summation orders.
 #pragma once
 #include <hip/hip_runtime.h>

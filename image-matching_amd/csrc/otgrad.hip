@@ -1,5 +1,5 @@
 // otgrad.hip -- the SuperGlue match loss (superglue/models/superglue_train.py:267-299) through the unrolled log-domain Sinkhorn, as value
-// and gradient (include/imx_otgrad.h).  Per pair, with C the (m+1) x (n+1) coupling matrix (never materialised:
+// and gradient (include/imx_train.h).  Per pair, with C the (m+1) x (n+1) coupling matrix (never materialised:
 // scores inside, bin_score in the last row and column):
 //
 //   forward   u_t = log_mu - LSE_j(C + v_{t-1}),  v_t = log_nu - LSE_i(C + u_t),  t = 1..T, every u_t and v_t kept    (2T launches)
@@ -15,6 +15,7 @@
 // row-strided partial sums (i ascending) added in ascending order, the loss and grad_bin 256 strided partial sums and a tree -- the
 // constants are compile-time, so equal inputs give equal bits whatever the batch, the padding or the workspace held before.
 #include "otgrad.h"
+#include "train_dev.h"
 
 namespace imx {
 namespace {
@@ -51,10 +52,6 @@ __device__ inline size_t vrow(const OtArgs& a, int b, int t) { return ((size_t)b
 
 __device__ inline float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ inline float wave_sum(float v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
 }
 
@@ -287,8 +284,6 @@ __global__ __launch_bounds__(256) void ot_bin_kernel(OtArgs a) {
   }
   if (t == 0) a.grad_bin[b] = part[0];
 }
-
-inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 }  // namespace
 

@@ -43,7 +43,7 @@ class Engine:
 
     def __init__(self, sp_cfg, sg_cfg, device, sp_variant=L.SP_VARIANT_BN, align_corners=None):
         self.lib = L.load_library()
-        self.spt = L.load_sptrain_library()        # the descriptor-training stages (include/imx_sptrain.h), on the same handle
+        self.train = L.load_train_library()        # the training stages (include/imx_train.h), on the same handle
         if not torch.cuda.is_available():
             raise ImxError("image_matching_amd needs a ROCm GPU (torch.cuda.is_available() is False); "
                            "there is no CPU fallback on the product path")
@@ -558,7 +558,7 @@ class Engine:
         labels = torch.empty(B, int(H), int(W), dtype=torch.float32, device=self.device)
         res = torch.empty(B, 2, int(H), int(W), dtype=torch.float32, device=self.device) if want_res else None
         flag = torch.empty(1, dtype=torch.int32, device=self.device)
-        self._check(self.spt.imx_warp_labels(self.handle, _ptr(pts), _ptr(counts), B, K, _ptr(mats), int(H), int(W), _ptr(labels), _ptr(res),
+        self._check(self.train.imx_warp_labels(self.handle, _ptr(pts), _ptr(counts), B, K, _ptr(mats), int(H), int(W), _ptr(labels), _ptr(res),
                                              _ptr(flag), _stream(self.device)))
         return labels, res, flag
 
@@ -568,7 +568,7 @@ class Engine:
         B, H, W = (int(v) for v in mask.shape)
         mask = self._f32(mask, (B, H, W), "erode_mask: mask")
         out = torch.empty_like(mask)
-        self._check(self.spt.imx_erode_mask(self.handle, _ptr(mask), _ptr(out), B, H, W, int(radius), _stream(self.device)))
+        self._check(self.train.imx_erode_mask(self.handle, _ptr(mask), _ptr(out), B, H, W, int(radius), _stream(self.device)))
         return out
 
     def detector_loss(self, semi, labels, mask, loss_type="softmax"):
@@ -583,7 +583,7 @@ class Engine:
         labels = self._f32(labels.reshape(B, Hc * 8, Wc * 8), (B, Hc * 8, Wc * 8), "detector_loss: labels")
         mask = self._f32(mask.reshape(B, Hc * 8, Wc * 8), (B, Hc * 8, Wc * 8), "detector_loss: mask")
         out = torch.empty(2, dtype=torch.float32, device=self.device)
-        self._check(self.spt.imx_detector_loss(self.handle, _ptr(semi), _ptr(labels), _ptr(mask), B, Hc * 8, Wc * 8, _ptr(out),
+        self._check(self.train.imx_detector_loss(self.handle, _ptr(semi), _ptr(labels), _ptr(mask), B, Hc * 8, Wc * 8, _ptr(out),
                                                _stream(self.device)))
         return out
 
@@ -599,7 +599,7 @@ class Engine:
         hcell = self._cell_mats(homographies, B, Hc, Wc, cell_space)
         pairs = torch.empty(B, int(Hc) * int(Wc), 2, dtype=torch.int32, device=self.device)
         n_valid = torch.empty(B, dtype=torch.int32, device=self.device)
-        self._check(self.spt.imx_desc_pairs(self.handle, _ptr(hcell), B, int(Hc), int(Wc), _ptr(pairs), _ptr(n_valid), _stream(self.device)))
+        self._check(self.train.imx_desc_pairs(self.handle, _ptr(hcell), B, int(Hc), int(Wc), _ptr(pairs), _ptr(n_valid), _stream(self.device)))
         return pairs, n_valid
 
     def desc_loss_sparse(self, desc_a, desc_b, homographies, choice, nonmatch_b, lamda_d=250., margin=0.2, method="1d", want_pairs=False,
@@ -623,7 +623,7 @@ class Engine:
                "flag": torch.empty(1, dtype=torch.int32, device=self.device)}
         if want_pairs:
             res["pairs"] = torch.empty(B, Hc * Wc, 2, dtype=torch.int32, device=self.device)
-        self._check(self.spt.imx_desc_loss_sparse(self.handle, _ptr(desc_a), _ptr(desc_b), B, d, Hc, Wc, _ptr(hcell), _ptr(choice), _ptr(nonmatch_b),
+        self._check(self.train.imx_desc_loss_sparse(self.handle, _ptr(desc_a), _ptr(desc_b), B, d, Hc, Wc, _ptr(hcell), _ptr(choice), _ptr(nonmatch_b),
                                                   M, R, float(lamda_d), float(margin), 1 if method == "1d" else 2, _ptr(res["out"]),
                                                   _ptr(res["mean"]), _ptr(res.get("pairs")), _ptr(res["flag"]), _stream(self.device)))
         return res
@@ -658,14 +658,7 @@ class Engine:
                 "warped_img": x[B:], "valid_mask": valid_mask, "warped_valid_mask": warped_mask, "semi": semi[:B], "semi_warp": semi[B:],
                 "coarse_desc": desc[:B], "coarse_desc_warp": desc[B:], "flag": flag}
 
-    # ------------------------------------------------------------------ gradients of the two training losses (include/imx_spgrad.h)
-    @property
-    def spg(self):
-        """libimx_spgrad.so, loaded on the first use of a gradient method"""
-        if getattr(self, "_spg", None) is None:
-            self._spg = L.load_spgrad_library()
-        return self._spg
-
+    # ------------------------------------------------------------------ gradients of the two training losses (include/imx_train.h)
     def _gout(self, gout):
         if gout is None:
             return None
@@ -676,7 +669,7 @@ class Engine:
     def detector_loss_grad(self, semi, labels, mask, gout=None, loss_type="softmax"):
         """detector_loss and its derivative with respect to semi in one call: returns (out (2) = {loss, sum of the cell masks},
         grad_semi (B,65,H/8,W/8) = gout d loss / d semi).  gout: a device scalar (or a number), None = 1.  The derivative is that of the
-        conditioned form the library evaluates (include/imx_spgrad.h)."""
+        conditioned form the library evaluates (include/imx_train.h)."""
         if loss_type != "softmax":
             raise NotImplementedError(f"detector_loss_grad: only loss_type 'softmax' (the shipped yaml) is served, got {loss_type!r}")
         B, C, Hc, Wc = (int(v) for v in semi.shape)
@@ -688,7 +681,7 @@ class Engine:
         gout = self._gout(gout)
         out = torch.empty(2, dtype=torch.float32, device=self.device)
         grad = torch.empty(B, 65, Hc, Wc, dtype=torch.float32, device=self.device)
-        self._check(self.spg.imx_detector_loss_grad(self.handle, _ptr(semi), _ptr(labels), _ptr(mask), B, Hc * 8, Wc * 8, _ptr(gout), _ptr(out),
+        self._check(self.train.imx_detector_loss_grad(self.handle, _ptr(semi), _ptr(labels), _ptr(mask), B, Hc * 8, Wc * 8, _ptr(gout), _ptr(out),
                                                     _ptr(grad), _stream(self.device)))
         return out, grad
 
@@ -715,7 +708,7 @@ class Engine:
                "grad_b": torch.empty(B, d, Hc, Wc, dtype=torch.float32, device=self.device)}
         if want_pairs:
             res["pairs"] = torch.empty(B, Hc * Wc, 2, dtype=torch.int32, device=self.device)
-        self._check(self.spg.imx_desc_loss_sparse_grad(self.handle, _ptr(desc_a), _ptr(desc_b), B, d, Hc, Wc, _ptr(hcell), _ptr(choice),
+        self._check(self.train.imx_desc_loss_sparse_grad(self.handle, _ptr(desc_a), _ptr(desc_b), B, d, Hc, Wc, _ptr(hcell), _ptr(choice),
                                                        _ptr(nonmatch_b), M, R, float(lamda_d), float(margin), 1 if method == "1d" else 2,
                                                        _ptr(gout), _ptr(res["out"]), _ptr(res["mean"]), _ptr(res.get("pairs")), _ptr(res["flag"]),
                                                        _ptr(res["grad_a"]), _ptr(res["grad_b"]), _stream(self.device)))
@@ -750,14 +743,7 @@ class Engine:
                 "coarse_desc": desc[:B], "coarse_desc_warp": desc[B:], "flag": flag, "grad_semi": g_semi, "grad_semi_warp": g_semi_w,
                 "grad_desc": g_a, "grad_desc_warp": g_b}
 
-    # ------------------------------------------------------------------ the SuperGlue match loss and its gradient (include/imx_otgrad.h)
-    @property
-    def otg(self):
-        """libimx_otgrad.so, loaded on the first use"""
-        if getattr(self, "_otg", None) is None:
-            self._otg = L.load_otgrad_library()
-        return self._otg
-
+    # ------------------------------------------------------------------ the SuperGlue match loss and its gradient (include/imx_train.h)
     def ot_match_loss_grad(self, scores, bin_score, all_matches, n_all, iters, n0=None, n1=None, gout=None, want_grad=True):
         """The objective of superglue/models/superglue_train.py:271-299 on a score matrix, with its derivative through the unrolled
         Sinkhorn: scores (B,N0,N1) fp32, bin_score a one-element fp32 device tensor (or a number), all_matches (B,2,L) int64 and n_all (B)
@@ -790,19 +776,12 @@ class Engine:
         if want_grad:
             res["grad_scores"] = torch.empty(B, N0, N1, dtype=torch.float32, device=dev)
             res["grad_bin"] = torch.empty(B, dtype=torch.float32, device=dev)
-        self._check(self.otg.imx_ot_match_loss_grad(self.handle, B, _ptr(scores), N0, N1, _ptr(n0), _ptr(n1), _ptr(bin_score), int(iters),
+        self._check(self.train.imx_ot_match_loss_grad(self.handle, B, _ptr(scores), N0, N1, _ptr(n0), _ptr(n1), _ptr(bin_score), int(iters),
                                                     _ptr(all_matches), _ptr(n_all), Lc, _ptr(gout), _ptr(res["loss"]),
                                                     _ptr(res.get("grad_scores")), _ptr(res.get("grad_bin")), _ptr(res["flag"]), _stream(dev)))
         return res
 
-    # ------------------------------------------------------------------ the GNN's attention, training form (include/imx_mhagrad.h)
-    @property
-    def mhg(self):
-        """libimx_mhagrad.so, loaded on the first use"""
-        if getattr(self, "_mhg", None) is None:
-            self._mhg = L.load_mhagrad_library()
-        return self._mhg
-
+    # ------------------------------------------------------------------ the GNN's attention, training form (include/imx_train.h)
     def _mha_shapes(self, who, q, k, v):
         """(B, D, H, N, M) of q (B,D,H,N) and k, v (B,D,H,M), the reference's view(B, dim, heads, -1)"""
         if q.dim() != 4 or k.dim() != 4:
@@ -825,7 +804,7 @@ class Engine:
         res = {"out": torch.empty(B, D, H, N, dtype=torch.float32, device=dev)}
         if want_lse:
             res["lse"] = torch.empty(B, H, N, dtype=torch.float32, device=dev)
-        self._check(self.mhg.imx_mha_forward_train(self.handle, B, H, D, N, M, _ptr(q), _ptr(k), _ptr(v), _ptr(nq), _ptr(nk),
+        self._check(self.train.imx_mha_forward_train(self.handle, B, H, D, N, M, _ptr(q), _ptr(k), _ptr(v), _ptr(nq), _ptr(nk),
                                                    _ptr(res["out"]), _ptr(res.get("lse")), _stream(dev)))
         return res
 
@@ -845,18 +824,11 @@ class Engine:
         for name, w, n in (("dq", want[0], N), ("dk", want[1], M), ("dv", want[2], M)):
             if w:
                 res[name] = torch.empty(B, D, H, n, dtype=torch.float32, device=dev)
-        self._check(self.mhg.imx_mha_backward(self.handle, B, H, D, N, M, _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(dout),
+        self._check(self.train.imx_mha_backward(self.handle, B, H, D, N, M, _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(dout),
                                               _ptr(nq), _ptr(nk), _ptr(res.get("dq")), _ptr(res.get("dk")), _ptr(res.get("dv")), _stream(dev)))
         return res
 
-    # ------------------------------------------------------------------ the 1x1 convolutions, training form (include/imx_lingrad.h)
-    @property
-    def ling(self):
-        """libimx_lingrad.so, loaded on the first use"""
-        if getattr(self, "_ling", None) is None:
-            self._ling = L.load_lingrad_library()
-        return self._ling
-
+    # ------------------------------------------------------------------ the 1x1 convolutions, training form (include/imx_train.h)
     def _conv1x1_args(self, who, x0, w, x1):
         """(B, Cout, C0, C1, N) of x0 (B,C0,N), x1 (B,C1,N) or None, w (Cout, C0+C1) or the (Cout, C0+C1, 1) parameter itself; every
         tensor a contiguous fp32 cuda tensor, otherwise ImxError (no silent copy)"""
@@ -881,7 +853,7 @@ class Engine:
             bias = self._f32(bias, (Cout,), "conv1x1_forward_train: bias")
         n = self._counts(n, B, "conv1x1_forward_train: n")
         res = {"y": torch.empty(B, Cout, N, dtype=torch.float32, device=dev)}
-        self._check(self.ling.imx_conv1x1_forward_train(self.handle, B, Cout, C0, C1, N, _ptr(x0), _ptr(x1), _ptr(w), _ptr(bias), _ptr(n),
+        self._check(self.train.imx_conv1x1_forward_train(self.handle, B, Cout, C0, C1, N, _ptr(x0), _ptr(x1), _ptr(w), _ptr(bias), _ptr(n),
                                                         _ptr(res["y"]), _stream(dev)))
         return res
 
@@ -903,19 +875,12 @@ class Engine:
                                     ("dw", want[2], tuple(w.shape)), ("db", want[3], (Cout,))):
             if wanted:
                 res[name] = torch.empty(shape, dtype=torch.float32, device=dev)
-        self._check(self.ling.imx_conv1x1_backward(self.handle, B, Cout, C0, C1, N, _ptr(x0), _ptr(x1), _ptr(w), _ptr(dy), _ptr(n),
+        self._check(self.train.imx_conv1x1_backward(self.handle, B, Cout, C0, C1, N, _ptr(x0), _ptr(x1), _ptr(w), _ptr(dy), _ptr(n),
                                                    _ptr(res.get("dx0")), _ptr(res.get("dx1")), _ptr(res.get("dw")), _ptr(res.get("db")),
                                                    _stream(dev)))
         return res
 
-    # ------------------------------------------------------------------ BatchNorm1d + ReLU, training form (include/imx_bngrad.h)
-    @property
-    def bng(self):
-        """libimx_bngrad.so, loaded on the first use"""
-        if getattr(self, "_bng", None) is None:
-            self._bng = L.load_bngrad_library()
-        return self._bng
-
+    # ------------------------------------------------------------------ BatchNorm1d + ReLU, training form (include/imx_train.h)
     def _bn_args(self, who, x, per_channel, full=()):
         """(B, C, N) of x (B,C,N); per_channel: (tensor or None, name) of shape (C), full: (tensor, name) of x's shape; every tensor a
         contiguous fp32 cuda tensor, otherwise ImxError (no silent copy)"""
@@ -948,7 +913,7 @@ class Engine:
         n = self._counts(n, B, "bn_relu_forward_train: n")
         res = {"y": torch.empty(B, C, N, dtype=torch.float32, device=dev), "mean": torch.empty(C, dtype=torch.float32, device=dev),
                "rstd": torch.empty(C, dtype=torch.float32, device=dev)}
-        self._check(self.bng.imx_bn_relu_forward_train(self.handle, B, C, N, 1 if training else 0, float(eps), float(momentum), _ptr(x), _ptr(gamma),
+        self._check(self.train.imx_bn_relu_forward_train(self.handle, B, C, N, 1 if training else 0, float(eps), float(momentum), _ptr(x), _ptr(gamma),
                                                        _ptr(beta), _ptr(n), _ptr(running_mean), _ptr(running_var), _ptr(num_batches_tracked),
                                                        _ptr(res["y"]), _ptr(res["mean"]), _ptr(res["rstd"]), _stream(dev)))
         return res
@@ -968,7 +933,7 @@ class Engine:
         for name, wanted, shape in (("dx", want[0], (B, C, N)), ("dgamma", want[1], (C,)), ("dbeta", want[2], (C,))):
             if wanted:
                 res[name] = torch.empty(shape, dtype=torch.float32, device=dev)
-        self._check(self.bng.imx_bn_relu_backward(self.handle, B, C, N, 1 if training else 0, _ptr(x), _ptr(gamma), _ptr(beta), _ptr(mean),
+        self._check(self.train.imx_bn_relu_backward(self.handle, B, C, N, 1 if training else 0, _ptr(x), _ptr(gamma), _ptr(beta), _ptr(mean),
                                                   _ptr(rstd), _ptr(dy), _ptr(n), _ptr(res.get("dx")), _ptr(res.get("dgamma")),
                                                   _ptr(res.get("dbeta")), _stream(dev)))
         return res

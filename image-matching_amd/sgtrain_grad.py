@@ -1,5 +1,5 @@
 """The SuperGlue training objective as a differentiable torch function whose value AND gradient come from libimx
-(include/imx_otgrad.h): the optimal-transport layer and the match loss of the reference's SuperGlue.forward
+(include/imx_train.h): the optimal-transport layer and the match loss of the reference's SuperGlue.forward
 (superglue/models/superglue_train.py:271-299) under PyTorch-ROCm.  The library supplies the cotangents at the score matrix and at
 bin_score, differentiated through the unrolled Sinkhorn as the reference's autograd does; PyTorch runs the backward of the einsum and of
 the network.
@@ -8,7 +8,7 @@ the network.
     loss = match_loss(engine, scores, self.bin_score, all_matches, n_all, iters).mean()
     loss.backward()
 
-The attention of the GNN (superglue_train.py:82-86) is here as well, forward and backward from libimx (include/imx_mhagrad.h): inside the
+The attention of the GNN (superglue_train.py:82-86) is here as well, forward and backward from libimx (include/imx_train.h): inside the
 reference's MultiHeadedAttention.forward,
 
     x, _ = attention(engine, query, key, value)
@@ -16,7 +16,7 @@ reference's MultiHeadedAttention.forward,
 keeps O(B H N) floats per layer for the backward instead of the (B, H, N, M) probabilities.
 
 The 1x1 convolutions around it (superglue_train.py:52, 96, 97, 111) are here too, forward and backward from libimx
-(include/imx_lingrad.h): inside MultiHeadedAttention.forward and MLP,
+(include/imx_train.h): inside MultiHeadedAttention.forward and MLP,
 
     y = conv1d(engine, x, conv.weight, conv.bias)                # nn.Conv1d(kernel_size=1)
     y = conv1d(engine, x, conv.weight, conv.bias, x1=message)    # the same on torch.cat([x, message], 1), never formed
@@ -25,7 +25,7 @@ and a whole layer of the GNN, `delta0 = attentional_propagation(engine, layer, d
 AttentionalGNN.forward: every matrix product in libimx, BatchNorm and ReLU PyTorch's.
 
 BatchNorm1d followed by ReLU (superglue_train.py:55-56, inside every MLP) is here as well, one launch forward and one backward
-(include/imx_bngrad.h): `h = batchnorm_relu(engine, bn, h)` for `relu(bn(h))`, `mlp(engine, seq, x)` for a whole Sequential that the
+(include/imx_train.h): `h = batchnorm_relu(engine, bn, h)` for `relu(bn(h))`, `mlp(engine, seq, x)` for a whole Sequential that the
 reference's MLP() built, `keypoint_encoder(engine, kenc, kpts, scores)` for `kenc(kpts, scores)`, and `gnn_layer(engine, layer, desc0,
 src0, n=n0, ns=n1)` for `layer(desc0, src0)` with everything in libimx -- and with per-pair counts, so a padded batch of pairs with
 different keypoint counts goes through a layer: the BatchNorm statistics are those of the valid columns only.

@@ -1,5 +1,5 @@
 """The two SuperPoint training losses as differentiable torch functions whose value AND gradient come from libimx
-(include/imx_spgrad.h): the label, mask and loss half of a training step of the reference's SuperPointNet under PyTorch-ROCm.  The
+(include/imx_train.h): the label, mask and loss half of a training step of the reference's SuperPointNet under PyTorch-ROCm.  The
 library supplies the cotangents at the network's outputs (semi, desc); PyTorch runs the network's own backward.
 
     loss = total_loss(engine, semi, semi_warp, desc, desc_warp, sample, lambda_loss)

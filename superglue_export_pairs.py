@@ -8,7 +8,7 @@ Per image of <image_path>/train: a random perspective warp, SuperPoint on both i
 (--pretrain_weights indoor | outdoor, or --superglue_checkpoint <file with a 'net' entry>) the same pass scores them: mean loss
 (superglue_train.py:289-299), precision and recall of matches0 against the ground truth.  There is no backward pass here: train
 with the reference's module on the exported pairs, validate checkpoints here.  --grads prints, beside the loss, the norms of its gradient at the
-score matrix and at bin_score through the unrolled Sinkhorn (include/imx_otgrad.h), on the forward's own score matrix copied out of the
+score matrix and at bin_score through the unrolled Sinkhorn (include/imx_train.h), on the forward's own score matrix copied out of the
 workspace (the debug tap 'scores_in': a host round trip, this is a validation tool); the backward of the network's layers is PyTorch's.
 
 The SuperPoint and SuperGlue flags are those of superpoint_glue_train.py; --out_dir, --batch, --seed, --superglue_checkpoint, --grads and

@@ -5,7 +5,7 @@ N synthetic images whose pseudo-labels come from homographic adaptation (export_
 
     python superpoint_validate_descriptor.py --synthetic 2 --size 120 160
 
---grads prints the norms of the loss gradients at the network's outputs as well (include/imx_spgrad.h).  The backward of the network's
+--grads prints the norms of the loss gradients at the network's outputs as well (include/imx_train.h).  The backward of the network's
 own layers is not here: training itself stays with the reference, which may take those cotangents."""
 import argparse
 import json

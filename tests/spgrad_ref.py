@@ -89,7 +89,7 @@ def desc_loss_t(da, db, pair_a, pair_b, choice, nonmatch_b, lamda_d=250., margin
         ma, mb = a1, fb[ib]
     match = torch.clamp(1 - (ma * mb).sum(-1), min=0).sum() / len(ia)
     prod = (a1[:, None, :] * fb[torch.as_tensor(np.asarray(nonmatch_b, np.int64)).to(da.device)]).sum(-1)
-    # the non-match hinge is strict (imx_spgrad.h): an entry with v = 0 exactly is no hard negative and carries no gradient.  (torch's
+    # the non-match hinge is strict (imx_train.h): an entry with v = 0 exactly is no hard negative and carries no gradient.  (torch's
     # clamp(min=0) would pass the gradient there; the fixtures hold no product within 1e-5 of the margin, so the two cannot differ on them.)
     v = torch.where(prod - margin > 0, prod - margin, torch.zeros_like(prod))
     hard = int((v != 0).sum())                                           # a constant of the derivative

@@ -204,6 +204,25 @@ def test_ragged_batch_and_the_two_forms(eng):
     assert np.array_equal(one["mean"], full[0][1, :, 0]) and np.allclose(one["rstd"], R.EPS ** -0.5, rtol=1e-6) and not one["dx"].any()
 
 
+def test_the_form_is_reported_per_launch_and_does_not_leak(eng):
+    """one handle with timing on: BatchNorm at (1, 2, 8) (one slot per thread: the register form), a 1x1 convolution, BatchNorm at
+    (1, 2, 4097) (17 slots, past kBnSlots = 16: the form that reads x again).  The report names the form of each BatchNorm launch, and
+    the convolution between them, whose launcher has one form and reports none, shows an empty one.  This records how the one
+    form slot behind the training entry points behaves (run() resets it per launch); separate slots per stage would pass it too"""
+    z = lambda *shape: torch.zeros(*shape, device="cuda")
+    eng.timing_reset()
+    eng.set_timing(True)
+    try:
+        eng.bn_relu_forward_train(z(1, 2, 8), z(2), z(2))
+        eng.conv1x1_forward_train(z(1, 4, 8), z(2, 4), None)
+        eng.bn_relu_forward_train(z(1, 2, 4097), z(2), z(2))
+        rows = [(name, launches, form) for name, launches, _, form in eng.timing_report(forms=True)]
+    finally:
+        eng.set_timing(False)
+        eng.timing_reset()
+    assert rows == [("bn_relu_fwd", 1, "regs"), ("lin_fwd", 1, ""), ("bn_relu_fwd", 1, "reread")], rows
+
+
 def test_equal_bits_between_calls_and_handles(eng):
     inputs, n = ragged_batch(300)
     first = call(eng, *inputs, n)
@@ -271,7 +290,7 @@ def test_errors_are_reported_and_the_handle_survives(eng):
             eng.bn_relu_forward_train(x, z(shape[1]), z(shape[1]))
         with pytest.raises(ImxError, match="bad shape"):
             eng.bn_relu_backward(x, z(shape[1]), z(shape[1]), z(shape[1]), z(shape[1]), z(*shape))
-    lib, x, c, y = eng.bng, z(2, 4, 8), z(4), z(2, 4, 8)
+    lib, x, c, y = eng.train, z(2, 4, 8), z(4), z(2, 4, 8)
     p = lambda t: None if t is None else t.data_ptr()
     err = lambda: eng.lib.imx_last_error(eng.handle)
     fwd = lambda B=2, C=4, N=8, train=1, eps=1e-5, mom=0.1, xx=x, g=c, b=c, rm=None, rv=None, yy=y, m=c, r=c: lib.imx_bn_relu_forward_train(

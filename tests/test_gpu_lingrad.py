@@ -251,7 +251,7 @@ def test_errors_are_reported_and_the_handle_survives(eng):
         eng.conv1x1_forward_train(z(1, 3, 4).transpose(1, 2), z(2, 4))
     with pytest.raises(ImxError, match=r"w must be \(Cout,4\)"):
         eng.conv1x1_forward_train(z(1, 4, 3), z(2, 5))
-    lib, x, w_, y = eng.ling, z(1, 4, 8), z(2, 4), z(1, 2, 8)
+    lib, x, w_, y = eng.train, z(1, 4, 8), z(2, 4), z(1, 2, 8)
     p = lambda t: t.data_ptr()
     err = lambda: eng.lib.imx_last_error(eng.handle)
     assert lib.imx_conv1x1_forward_train(eng.handle, 1, 2, 4, 0, 8, p(x), p(x), p(w_), None, None, p(y), None) != 0 and b"x1 given with C1 = 0" in err()

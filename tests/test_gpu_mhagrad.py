@@ -227,7 +227,7 @@ def test_errors_are_reported_and_the_handle_survives(eng):
         eng.mha_forward_train(z(0, 32, 4, 8), z(0, 32, 4, 8), z(0, 32, 4, 8))
     with pytest.raises(ImxError, match="bad shape"):
         eng.mha_backward(z(0, 32, 4, 8), z(0, 32, 4, 8), z(0, 32, 4, 8), z(0, 32, 4, 8), z(0, 4, 8), z(0, 32, 4, 8))
-    lib, t = eng.mhg, z(1, 32, 1, 8)
+    lib, t = eng.train, z(1, 32, 1, 8)
     p = lambda x: x.data_ptr()
     assert lib.imx_mha_forward_train(eng.handle, 1, 1, 32, 8, 8, None, p(t), p(t), None, None, p(t), None, None) != 0
     assert b"null argument" in eng.lib.imx_last_error(eng.handle)

@@ -1,10 +1,9 @@
 """The gradient of the SuperGlue match loss through the unrolled Sinkhorn, host side: the project's restatement (tests/otgrad_ref.py:
 the recursion of DESIGN.md section 13 written out, no autograd) against the samples, row and column sums the reference's own autograd
-wrote (tests/golden/make_golden_otgrad.py), against finite differences, and the declared entry points of the four libraries.  No GPU."""
+wrote (tests/golden/make_golden_otgrad.py), against finite differences, and the Python surface of the entry points.  No GPU."""
 import glob
 import inspect
 import os
-import re
 
 import numpy as np
 import pytest
@@ -14,9 +13,7 @@ from tests import otgrad_ref as O
 from tests import util
 from tests.golden.make_golden_otgrad import CASES, RAGGED_FRAME, sample_positions
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURES = sorted(os.path.basename(p) for p in glob.glob(os.path.join(util.GOLDEN, "otgrad_*.npz")))
-ENTRY_POINTS = ("imx_ot_match_loss_grad",)
 ITEMS = [(name, k) for name in CASES for k in range(len(CASES[name]))]
 
 
@@ -111,26 +108,9 @@ def test_list_rules_of_the_restatement():
 
 
 def test_entry_points_are_declared_and_bound():
-    """libimx_otgrad.so exports what include/imx_otgrad.h declares and nothing else; the tables of the other three libraries are untouched"""
-    import shutil
-    import subprocess
-    from image_matching_amd import _lib, sgtrain_grad
+    """the Python surface has the documented signatures; a CPU tensor is an error (the exported tables: tests/test_train_library_host.py)"""
+    from image_matching_amd import sgtrain_grad
     from image_matching_amd.engine import Engine
-    header = open(os.path.join(ROOT, "include", "imx_otgrad.h")).read()
-    declared = set(re.findall(r"^IMX_API [^\n]*?\b(imx_\w+)\(", header, re.M))
-    assert declared == set(ENTRY_POINTS) == set(_lib.OTGRAD_EXPORTS)
-    assert not declared & (set(_lib.EXPORTS) | set(_lib.SPTRAIN_EXPORTS) | set(_lib.SPGRAD_EXPORTS))
-    assert len(_lib.EXPORTS) == 34 and len(_lib.SPTRAIN_EXPORTS) == 5 and len(_lib.SPGRAD_EXPORTS) == 2
-    lib = _lib.load_otgrad_library()
-    for n in ENTRY_POINTS:
-        assert getattr(lib, n).argtypes is not None and len(getattr(lib, n).argtypes) == 18, n
-    if shutil.which("nm"):
-        def table(path):
-            out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-            return {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
-        assert table(_lib.OTGRAD_LIB_PATH) == declared
-        assert table(_lib.LIB_PATH) == set(_lib.EXPORTS) and table(_lib.SPTRAIN_LIB_PATH) == set(_lib.SPTRAIN_EXPORTS)
-        assert table(_lib.SPGRAD_LIB_PATH) == set(_lib.SPGRAD_EXPORTS)
     sig = lambda f: list(inspect.signature(f).parameters)
     assert sig(Engine.ot_match_loss_grad)[:9] == ["self", "scores", "bin_score", "all_matches", "n_all", "iters", "n0", "n1", "gout"]
     assert issubclass(sgtrain_grad.ot_match_loss, torch.autograd.Function)

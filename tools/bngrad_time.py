@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Times BatchNorm1d + ReLU of SuperGlue's MLPs in their training form (include/imx_bngrad.h) on the GPU at (B, C, N) in
+"""Times BatchNorm1d + ReLU of SuperGlue's MLPs in their training form (include/imx_train.h) on the GPU at (B, C, N) in
 {(1, 256, 1024), (8, 256, 1024), (1, 512, 2048), (8, 512, 2048), (1, 32, 1024)}, training mode.  HIP events on the stream, a warm-up, then
 the median of `--batches` (at least 20) batches, the variants alternating inside one process.  Per shape, each with the peak of torch's
 allocator above what was allocated before:

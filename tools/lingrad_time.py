@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Times the 1x1 convolutions of SuperGlue's GNN in their training form (include/imx_lingrad.h) on the GPU at B in {1, 8} times
+"""Times the 1x1 convolutions of SuperGlue's GNN in their training form (include/imx_train.h) on the GPU at B in {1, 8} times
 (Cout, C0, C1, N) in {(128, 128, 0, 1024), (256, 128, 128, 1024), (512, 256, 256, 2048)}.  HIP events on the stream, a warm-up, then the
 median of `--batches` (at least 20) batches, the variants alternating inside one process.  Per shape, each with the peak of torch's
 allocator above what was allocated before:

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Times the attention of SuperGlue's GNN in its training form (include/imx_mhagrad.h) on the GPU at (B, D, H, N = M) = (1, 32, 4, 1024),
+"""Times the attention of SuperGlue's GNN in its training form (include/imx_train.h) on the GPU at (B, D, H, N = M) = (1, 32, 4, 1024),
 (8, 32, 4, 1024) and (1, 64, 4, 2048).  HIP events on the stream, a warm-up, then the median of `--batches` (at least 20) batches, the
 variants alternating inside one process.  Per shape, each with the peak of torch's allocator above what was allocated before:
 

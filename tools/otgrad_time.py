@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Times the SuperGlue match loss through the unrolled Sinkhorn (include/imx_otgrad.h) on the GPU: B in {1, 8} at 1024 x 1024 / T = 30 and
+"""Times the SuperGlue match loss through the unrolled Sinkhorn (include/imx_train.h) on the GPU: B in {1, 8} at 1024 x 1024 / T = 30 and
 B = 1 at 2048 x 2048 / T = 100.  HIP events on the stream, a warm-up, then the median of `--batches` (at least 20) batches, the
 variants alternating inside one process.  Per shape, each with its peak device memory:
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Times the value-and-gradient calls of the two SuperPoint training losses (include/imx_spgrad.h) on the GPU: a batch of 8 warped pairs
+"""Times the value-and-gradient calls of the two SuperPoint training losses (include/imx_train.h) on the GPU: a batch of 8 warped pairs
 at 480 x 640, d = 128 and 256, M = 1000 matches x R = 100 non-matches.  HIP events on the stream, a warm-up, then the median of
 `--batches` (at least 20) batches, the variants alternating inside one process.  Per entry point:
 
