@@ -1,5 +1,5 @@
-"""ctypes binding of libimx.so (C ABI: include/imx.h) and libimx_train.so (include/imx_train.h).  There is no CPU fallback: if the
-library is missing or no GPU is present the product path raises."""
+"""ctypes binding of libimx.so (C ABI: include/imx.h), libimx_train.so (include/imx_train.h) and libimx_sgtrain.so
+(include/imx_sgtrain.h).  There is no CPU fallback: if the library is missing or no GPU is present the product path raises."""
 import ctypes
 import os
 
@@ -64,8 +64,18 @@ _TRAIN_ARGTYPES = {
 }
 TRAIN_EXPORTS = tuple(_TRAIN_ARGTYPES)
 
+# libimx_sgtrain.so (C ABI: include/imx_sgtrain.h): the score product of SuperGlue's training step, on libimx.so's handles -- a library of
+# its own because libimx_train.so's symbol table is pinned to imx_train.h; name -> argtypes, one line per entry point
+SGTRAIN_LIB_PATH = os.path.join(_HERE, "libimx_sgtrain.so")
+_SGTRAIN_ARGTYPES = {
+    "imx_score_product_forward_train": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp],
+    "imx_score_product_backward": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp],
+}
+SGTRAIN_EXPORTS = tuple(_SGTRAIN_ARGTYPES)
+
 _lib = None
 _train = None
+_sgtrain = None
 
 
 def load_library():
@@ -142,4 +152,19 @@ def load_train_library():
     for name, argtypes in _TRAIN_ARGTYPES.items():
         getattr(lib, name).argtypes = argtypes          # raises AttributeError if a declared symbol is missing
     _train = lib
+    return lib
+
+
+def load_sgtrain_library():
+    """Load libimx_sgtrain.so (built beside libimx.so by the same make); libimx.so is loaded first: it makes the handles."""
+    global _sgtrain
+    if _sgtrain is not None:
+        return _sgtrain
+    load_library()
+    if not os.path.exists(SGTRAIN_LIB_PATH):
+        raise RuntimeError(f"libimx_sgtrain.so not found at {SGTRAIN_LIB_PATH}: build it with `make -C image-matching_amd/csrc`")
+    lib = ctypes.CDLL(SGTRAIN_LIB_PATH)
+    for name, argtypes in _SGTRAIN_ARGTYPES.items():
+        getattr(lib, name).argtypes = argtypes          # raises AttributeError if a declared symbol is missing
+    _sgtrain = lib
     return lib

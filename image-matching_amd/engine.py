@@ -44,6 +44,7 @@ class Engine:
     def __init__(self, sp_cfg, sg_cfg, device, sp_variant=L.SP_VARIANT_BN, align_corners=None):
         self.lib = L.load_library()
         self.train = L.load_train_library()        # the training stages (include/imx_train.h), on the same handle
+        self.sgtrain = L.load_sgtrain_library()    # the score product of SuperGlue's training step (include/imx_sgtrain.h), likewise
         if not torch.cuda.is_available():
             raise ImxError("image_matching_amd needs a ROCm GPU (torch.cuda.is_available() is False); "
                            "there is no CPU fallback on the product path")
@@ -936,6 +937,50 @@ class Engine:
         self._check(self.train.imx_bn_relu_backward(self.handle, B, C, N, 1 if training else 0, _ptr(x), _ptr(gamma), _ptr(beta), _ptr(mean),
                                                   _ptr(rstd), _ptr(dy), _ptr(n), _ptr(res.get("dx")), _ptr(res.get("dgamma")),
                                                   _ptr(res.get("dbeta")), _stream(dev)))
+        return res
+
+    # ------------------------------------------------------------------ the score product, training form (include/imx_sgtrain.h)
+    def _score_args(self, who, a, b, scale, dscores=None):
+        """(B, D, N0, N1, scale) of a (B,D,N0) and b (B,D,N1); every tensor a contiguous fp32 cuda tensor, otherwise ImxError (no silent
+        copy); scale None = D ** -0.5"""
+        for t, what in ((a, "a"), (b, "b")) + (((dscores, "dscores"),) if dscores is not None else ()):
+            if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ImxError(f"{who}: {what} must be a contiguous fp32 cuda tensor")
+        if a.dim() != 3 or b.dim() != 3 or a.shape[0] != b.shape[0] or a.shape[1] != b.shape[1]:
+            raise ImxError(f"{who}: a and b must be (B,D,N0) and (B,D,N1), got {tuple(a.shape)} and {tuple(b.shape)}")
+        B, D, N0 = (int(s) for s in a.shape)
+        N1 = int(b.shape[2])
+        if dscores is not None and tuple(dscores.shape) != (B, N0, N1):
+            raise ImxError(f"{who}: dscores must be ({B},{N0},{N1}), got {tuple(dscores.shape)}")
+        return B, D, N0, N1, float(D) ** -0.5 if scale is None else float(scale)
+
+    def score_product_forward_train(self, a, b, n0=None, n1=None, scale=None):
+        """torch.einsum('bdn,bdm->bnm', a, b) * scale (superglue/models/superglue_train.py:267-268): a (B,D,N0), b (B,D,N1), n0 / n1 (B)
+        int32 counts or None = all, scale None = D ** -0.5, the reference's.  Returns dict: scores (B,N0,N1), 0 on rows past n0 and
+        columns past n1.  No host synchronisation."""
+        dev = self.device
+        B, D, N0, N1, scale = self._score_args("score_product_forward_train", a, b, scale)
+        n0, n1 = self._counts(n0, B, "score_product_forward_train: n0"), self._counts(n1, B, "score_product_forward_train: n1")
+        res = {"scores": torch.empty(B, N0, N1, dtype=torch.float32, device=dev)}
+        self._check(self.sgtrain.imx_score_product_forward_train(self.handle, B, D, N0, N1, _ptr(a), _ptr(b), _ptr(n0), _ptr(n1), scale,
+                                                                 _ptr(res["scores"]), _stream(dev)))
+        return res
+
+    def score_product_backward(self, a, b, dscores, n0=None, n1=None, scale=None, want=(True, True)):
+        """The backward of score_product_forward_train from dscores (B,N0,N1).  Returns dict with da (B,D,N0) and db (B,D,N1) (0 past the
+        counts), each only where `want` = (da, db) asks for it; a gradient's bits do not depend on whether the other is formed.  No host
+        synchronisation."""
+        dev = self.device
+        B, D, N0, N1, scale = self._score_args("score_product_backward", a, b, scale, dscores)
+        n0, n1 = self._counts(n0, B, "score_product_backward: n0"), self._counts(n1, B, "score_product_backward: n1")
+        if len(want) != 2:
+            raise ImxError(f"score_product_backward: want must be two flags (da, db), got {want!r}")
+        res = {}
+        for name, wanted, shape in (("da", want[0], (B, D, N0)), ("db", want[1], (B, D, N1))):
+            if wanted:
+                res[name] = torch.empty(shape, dtype=torch.float32, device=dev)
+        self._check(self.sgtrain.imx_score_product_backward(self.handle, B, D, N0, N1, _ptr(a), _ptr(b), _ptr(dscores), _ptr(n0), _ptr(n1), scale,
+                                                            _ptr(res.get("da")), _ptr(res.get("db")), _stream(dev)))
         return res
 
     # ------------------------------------------------------------------ kernel-form options (include/imx.h: imx_set_option)

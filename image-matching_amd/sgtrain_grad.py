@@ -30,6 +30,11 @@ reference's MLP() built, `keypoint_encoder(engine, kenc, kpts, scores)` for `ken
 src0, n=n0, ns=n1)` for `layer(desc0, src0)` with everything in libimx -- and with per-pair counts, so a padded batch of pairs with
 different keypoint counts goes through a layer: the BatchNorm statistics are those of the valid columns only.
 
+The score product between the two images' projected descriptors (superglue_train.py:267-268) is here too, forward and backward from
+libimx_sgtrain (include/imx_sgtrain.h): `scores(engine, mdesc0, mdesc1, n0, n1)` for `torch.einsum('bdn,bdm->bnm', mdesc0, mdesc1) /
+descriptor_dim ** .5`, with counts.  With it every matrix product of the training forward is the library's;
+sgtrain_model.SuperGlueTrainable composes the whole step.
+
 Inputs are contiguous fp32 cuda tensors; anything else raises (no silent copy, no CPU path)."""
 import torch
 from torch.autograd.function import once_differentiable
@@ -269,3 +274,37 @@ def gnn_layer(engine, layer, x, source, n=None, ns=None):
     m, _ = attention(engine, query, key, value, nq=n, nk=ns)
     message = conv1d(engine, m.view(b, attn.dim * attn.num_heads, -1), attn.merge.weight, attn.merge.bias, n=n)
     return mlp(engine, layer.mlp, x, x1=message, n=n)
+
+
+class score_product(torch.autograd.Function):
+    """score_product.apply(engine, mdesc0, mdesc1, n0, n1): torch.einsum('bdn,bdm->bnm', mdesc0, mdesc1) / D ** .5 on mdesc0 (B,D,N0)
+    and mdesc1 (B,D,N1), differentiable with respect to both.  Saved for the backward: mdesc0 and mdesc1 only.  n0 / n1 (B) int32 counts
+    of a padded batch or None."""
+
+    @staticmethod
+    def forward(ctx, engine, mdesc0, mdesc1, n0=None, n1=None):
+        for t, what in ((mdesc0, "mdesc0"), (mdesc1, "mdesc1")):
+            _require(t, f"score_product: {what}")
+        s = engine.score_product_forward_train(mdesc0, mdesc1, n0=n0, n1=n1)["scores"]
+        ctx.engine, ctx.n0, ctx.n1 = engine, n0, n1
+        ctx.save_for_backward(mdesc0, mdesc1)
+        return s
+
+    @staticmethod
+    @once_differentiable                                                 # the kernels form first derivatives only
+    def backward(ctx, grad_scores):
+        mdesc0, mdesc1 = ctx.saved_tensors
+        want = tuple(ctx.needs_input_grad[1:3])
+        if not any(want):
+            return (None,) * 5
+        grad_scores = grad_scores.contiguous()                           # (autograd's own tensor: it may hand over a view)
+        _require(grad_scores, "score_product: grad_scores")
+        g = ctx.engine.score_product_backward(mdesc0, mdesc1, grad_scores, n0=ctx.n0, n1=ctx.n1, want=want)
+        return None, g.get("da"), g.get("db"), None, None
+
+
+def scores(engine, mdesc0, mdesc1, n0=None, n1=None):
+    """torch.einsum('bdn,bdm->bnm', mdesc0, mdesc1) / descriptor_dim ** .5 of superglue_train.py:267-268; `.backward()` reaches mdesc0
+    and mdesc1 through the library's kernels.  n0 / n1 (B) int32: rows past n0[b] and columns past n1[b] are not read and come out as
+    0."""
+    return score_product.apply(engine, mdesc0, mdesc1, n0, n1)
