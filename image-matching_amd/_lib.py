@@ -1,5 +1,5 @@
-"""ctypes binding of libimx.so (C ABI: include/imx.h), libimx_train.so (include/imx_train.h) and libimx_sgtrain.so
-(include/imx_sgtrain.h).  There is no CPU fallback: if the library is missing or no GPU is present the product path raises."""
+"""ctypes binding of libimx.so (C ABI: include/imx.h), libimx_train.so (include/imx_train.h), libimx_sgtrain.so
+(include/imx_sgtrain.h) and libimx_spnet.so (include/imx_spnet.h).  There is no CPU fallback: if the library is missing or no GPU is present the product path raises."""
 import ctypes
 import os
 
@@ -73,9 +73,19 @@ _SGTRAIN_ARGTYPES = {
 }
 SGTRAIN_EXPORTS = tuple(_SGTRAIN_ARGTYPES)
 
+# libimx_spnet.so (C ABI: include/imx_spnet.h): the 3x3 convolutions of SuperPoint's training step, on libimx.so's handles -- a library of
+# its own because the other three symbol tables are pinned to their headers; name -> argtypes, one line per entry point
+SPNET_LIB_PATH = os.path.join(_HERE, "libimx_spnet.so")
+_SPNET_ARGTYPES = {
+    "imx_conv3x3_forward_train": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
+    "imx_conv3x3_backward": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+}
+SPNET_EXPORTS = tuple(_SPNET_ARGTYPES)
+
 _lib = None
 _train = None
 _sgtrain = None
+_spnet = None
 
 
 def load_library():
@@ -167,4 +177,19 @@ def load_sgtrain_library():
     for name, argtypes in _SGTRAIN_ARGTYPES.items():
         getattr(lib, name).argtypes = argtypes          # raises AttributeError if a declared symbol is missing
     _sgtrain = lib
+    return lib
+
+
+def load_spnet_library():
+    """Load libimx_spnet.so (built beside libimx.so by the same make); libimx.so is loaded first: it makes the handles."""
+    global _spnet
+    if _spnet is not None:
+        return _spnet
+    load_library()
+    if not os.path.exists(SPNET_LIB_PATH):
+        raise RuntimeError(f"libimx_spnet.so not found at {SPNET_LIB_PATH}: build it with `make -C image-matching_amd/csrc`")
+    lib = ctypes.CDLL(SPNET_LIB_PATH)
+    for name, argtypes in _SPNET_ARGTYPES.items():
+        getattr(lib, name).argtypes = argtypes          # raises AttributeError if a declared symbol is missing
+    _spnet = lib
     return lib

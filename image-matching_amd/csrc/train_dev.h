@@ -1,5 +1,6 @@
-// train_dev.h -- the helpers that more than one training kernel file of libimx_train.so uses with the same operations in the same order:
-// the operands and accumulator of v_mfma_f32_32x32x2_f32 (lin_train.hip, mha_train.hip), the butterfly sum over a wave (bn_train.hip,
+// train_dev.h -- the helpers that more than one training kernel file (libimx_train.so, libimx_sgtrain.so, libimx_spnet.so) uses with the
+// same operations in the same order: the operands and accumulator of v_mfma_f32_32x32x2_f32 (lin_train.hip, mha_train.hip,
+// score_train.hip, conv3_train.hip), the butterfly sum over a wave (bn_train.hip,
 // otgrad.hip) and the host's grid division.  Everything is inlined at its call: no symbol of a code object comes from here.
 #pragma once
 #include <hip/hip_runtime.h>

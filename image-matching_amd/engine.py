@@ -45,6 +45,7 @@ class Engine:
         self.lib = L.load_library()
         self.train = L.load_train_library()        # the training stages (include/imx_train.h), on the same handle
         self.sgtrain = L.load_sgtrain_library()    # the score product of SuperGlue's training step (include/imx_sgtrain.h), likewise
+        self.spnet = L.load_spnet_library()        # the 3x3 convolutions of SuperPoint's training step (include/imx_spnet.h), likewise
         if not torch.cuda.is_available():
             raise ImxError("image_matching_amd needs a ROCm GPU (torch.cuda.is_available() is False); "
                            "there is no CPU fallback on the product path")
@@ -981,6 +982,51 @@ class Engine:
                 res[name] = torch.empty(shape, dtype=torch.float32, device=dev)
         self._check(self.sgtrain.imx_score_product_backward(self.handle, B, D, N0, N1, _ptr(a), _ptr(b), _ptr(dscores), _ptr(n0), _ptr(n1), scale,
                                                             _ptr(res.get("da")), _ptr(res.get("db")), _stream(dev)))
+        return res
+
+    # ------------------------------------------------------------------ the 3x3 convolutions, training form (include/imx_spnet.h)
+    def _conv3x3_args(self, who, x, w, dy=None):
+        """(B, Cout, Cin, H, W) of x (B,Cin,H,W), w (Cout,Cin,3,3) and dy (B,Cout,H,W) or None; every tensor a contiguous fp32 cuda tensor,
+        otherwise ImxError (no silent copy)"""
+        for t, what in ((x, "x"), (w, "w")) + (((dy, "dy"),) if dy is not None else ()):
+            if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ImxError(f"{who}: {what} must be a contiguous fp32 cuda tensor")
+        if x.dim() != 4:
+            raise ImxError(f"{who}: x must be (B,Cin,H,W), got {tuple(x.shape)}")
+        B, Cin, H, W = (int(s) for s in x.shape)
+        if w.dim() != 4 or tuple(w.shape[1:]) != (Cin, 3, 3):
+            raise ImxError(f"{who}: w must be (Cout,{Cin},3,3), got {tuple(w.shape)}")
+        Cout = int(w.shape[0])
+        if dy is not None and tuple(dy.shape) != (B, Cout, H, W):
+            raise ImxError(f"{who}: dy must be ({B},{Cout},{H},{W}), got {tuple(dy.shape)}")
+        return B, Cout, Cin, H, W
+
+    def conv3x3_forward_train(self, x, w, bias=None):
+        """F.conv2d(x, w, bias, padding=1) for a 3x3 weight: x (B,Cin,H,W), w (Cout,Cin,3,3), bias (Cout) or None, NCHW in place.  Returns
+        dict: y (B,Cout,H,W).  No host synchronisation."""
+        dev = self.device
+        B, Cout, Cin, H, W = self._conv3x3_args("conv3x3_forward_train", x, w)
+        if bias is not None:
+            bias = self._f32(bias, (Cout,), "conv3x3_forward_train: bias")
+        res = {"y": torch.empty(B, Cout, H, W, dtype=torch.float32, device=dev)}
+        self._check(self.spnet.imx_conv3x3_forward_train(self.handle, B, Cout, Cin, H, W, _ptr(x), _ptr(w), _ptr(bias), _ptr(res["y"]),
+                                                        _stream(dev)))
+        return res
+
+    def conv3x3_backward(self, x, w, dy, want=(True, True, True)):
+        """The backward of conv3x3_forward_train from dy (B,Cout,H,W).  Returns dict with dx (B,Cin,H,W), dw (Cout,Cin,3,3) and db (Cout)
+        (overwritten, not accumulated), each only where `want` = (dx, dw, db) asks for it.  A gradient's bits do not depend on which others
+        are formed.  No host synchronisation."""
+        dev = self.device
+        B, Cout, Cin, H, W = self._conv3x3_args("conv3x3_backward", x, w, dy)
+        if len(want) != 3:
+            raise ImxError(f"conv3x3_backward: want must be three flags (dx, dw, db), got {want!r}")
+        res = {}
+        for name, wanted, shape in (("dx", want[0], (B, Cin, H, W)), ("dw", want[1], (Cout, Cin, 3, 3)), ("db", want[2], (Cout,))):
+            if wanted:
+                res[name] = torch.empty(shape, dtype=torch.float32, device=dev)
+        self._check(self.spnet.imx_conv3x3_backward(self.handle, B, Cout, Cin, H, W, _ptr(x), _ptr(w), _ptr(dy), _ptr(res.get("dx")),
+                                                   _ptr(res.get("dw")), _ptr(res.get("db")), _stream(dev)))
         return res
 
     # ------------------------------------------------------------------ kernel-form options (include/imx.h: imx_set_option)
