@@ -1,5 +1,5 @@
 """ctypes binding of libimx.so (C ABI: include/imx.h), libimx_train.so (include/imx_train.h), libimx_sgtrain.so
-(include/imx_sgtrain.h) and libimx_spnet.so (include/imx_spnet.h).  There is no CPU fallback: if the library is missing or no GPU is present the product path raises."""
+(include/imx_sgtrain.h), libimx_spnet.so (include/imx_spnet.h) and libimx_spnorm.so (include/imx_spnorm.h).  There is no CPU fallback: if the library is missing or no GPU is present the product path raises."""
 import ctypes
 import os
 
@@ -82,10 +82,20 @@ _SPNET_ARGTYPES = {
 }
 SPNET_EXPORTS = tuple(_SPNET_ARGTYPES)
 
+# libimx_spnorm.so (C ABI: include/imx_spnorm.h): BatchNorm2d [+ ReLU] of SuperPoint's training step on NCHW maps, on libimx.so's handles -- a
+# library of its own because the other four symbol tables are pinned to their headers; name -> argtypes, one line per entry point
+SPNORM_LIB_PATH = os.path.join(_HERE, "libimx_spnorm.so")
+_SPNORM_ARGTYPES = {
+    "imx_bn2d_forward_train": [_vp, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "imx_bn2d_backward": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+}
+SPNORM_EXPORTS = tuple(_SPNORM_ARGTYPES)
+
 _lib = None
 _train = None
 _sgtrain = None
 _spnet = None
+_spnorm = None
 
 
 def load_library():
@@ -192,4 +202,19 @@ def load_spnet_library():
     for name, argtypes in _SPNET_ARGTYPES.items():
         getattr(lib, name).argtypes = argtypes          # raises AttributeError if a declared symbol is missing
     _spnet = lib
+    return lib
+
+
+def load_spnorm_library():
+    """Load libimx_spnorm.so (built beside libimx.so by the same make); libimx.so is loaded first: it makes the handles."""
+    global _spnorm
+    if _spnorm is not None:
+        return _spnorm
+    load_library()
+    if not os.path.exists(SPNORM_LIB_PATH):
+        raise RuntimeError(f"libimx_spnorm.so not found at {SPNORM_LIB_PATH}: build it with `make -C image-matching_amd/csrc`")
+    lib = ctypes.CDLL(SPNORM_LIB_PATH)
+    for name, argtypes in _SPNORM_ARGTYPES.items():
+        getattr(lib, name).argtypes = argtypes          # raises AttributeError if a declared symbol is missing
+    _spnorm = lib
     return lib

@@ -46,6 +46,7 @@ class Engine:
         self.train = L.load_train_library()        # the training stages (include/imx_train.h), on the same handle
         self.sgtrain = L.load_sgtrain_library()    # the score product of SuperGlue's training step (include/imx_sgtrain.h), likewise
         self.spnet = L.load_spnet_library()        # the 3x3 convolutions of SuperPoint's training step (include/imx_spnet.h), likewise
+        self.spnorm = L.load_spnorm_library()      # BatchNorm2d [+ ReLU] of SuperPoint's training step (include/imx_spnorm.h), likewise
         if not torch.cuda.is_available():
             raise ImxError("image_matching_amd needs a ROCm GPU (torch.cuda.is_available() is False); "
                            "there is no CPU fallback on the product path")
@@ -1027,6 +1028,64 @@ class Engine:
                 res[name] = torch.empty(shape, dtype=torch.float32, device=dev)
         self._check(self.spnet.imx_conv3x3_backward(self.handle, B, Cout, Cin, H, W, _ptr(x), _ptr(w), _ptr(dy), _ptr(res.get("dx")),
                                                    _ptr(res.get("dw")), _ptr(res.get("db")), _stream(dev)))
+        return res
+
+    # ------------------------------------------------------------------ BatchNorm2d [+ ReLU], training form (include/imx_spnorm.h)
+    def _bn2d_args(self, who, x, per_channel, dy=None):
+        """(B, C, HW) of x (B,C,H,W); per_channel: (tensor or None, name) of shape (C); dy of x's shape or None; every tensor a contiguous
+        fp32 cuda tensor, otherwise ImxError (no silent copy)"""
+        for t, what in ((x, "x"),) + (((dy, "dy"),) if dy is not None else ()) + tuple(p for p in per_channel if p[0] is not None):
+            if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ImxError(f"{who}: {what} must be a contiguous fp32 cuda tensor")
+        if x.dim() != 4:
+            raise ImxError(f"{who}: x must be (B,C,H,W), got {tuple(x.shape)}")
+        B, C, H, W = (int(s) for s in x.shape)
+        if dy is not None and tuple(dy.shape) != (B, C, H, W):
+            raise ImxError(f"{who}: dy must be ({B},{C},{H},{W}), got {tuple(dy.shape)}")
+        for t, what in per_channel:
+            if t is not None and tuple(t.shape) != (C,):
+                raise ImxError(f"{who}: {what} must be ({C},), got {tuple(t.shape)}")
+        return B, C, H * W
+
+    def bn2d_forward_train(self, x, gamma, beta, running_mean=None, running_var=None, num_batches_tracked=None, relu=True, training=True,
+                           momentum=0.1, eps=1e-5):
+        """F.batch_norm(x, running_mean, running_var, gamma, beta, training, momentum, eps) on x (B,C,H,W), NCHW in place, followed by F.relu
+        when `relu`.  In training mode running_mean / running_var (C) and num_batches_tracked (one int64) are updated in place where given;
+        in evaluation mode the running statistics are required.  Returns dict: y (B,C,H,W), mean and rstd (C), what bn2d_backward needs
+        beside x.  No host synchronisation."""
+        dev = self.device
+        B, C, HW = self._bn2d_args("bn2d_forward_train", x, ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"),
+                                                             (running_var, "running_var")))
+        if gamma is None or beta is None:
+            raise ImxError("bn2d_forward_train: gamma and beta are required")
+        if num_batches_tracked is not None and (not isinstance(num_batches_tracked, torch.Tensor) or num_batches_tracked.device.type != "cuda"
+                                                or num_batches_tracked.dtype != torch.int64 or num_batches_tracked.numel() != 1):
+            raise ImxError("bn2d_forward_train: num_batches_tracked must be a cuda int64 tensor of one element")
+        res = {"y": torch.empty_like(x), "mean": torch.empty(C, dtype=torch.float32, device=dev),
+               "rstd": torch.empty(C, dtype=torch.float32, device=dev)}
+        self._check(self.spnorm.imx_bn2d_forward_train(self.handle, B, C, HW, 1 if relu else 0, 1 if training else 0, float(eps), float(momentum),
+                                                       _ptr(x), _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var),
+                                                       _ptr(num_batches_tracked), _ptr(res["y"]), _ptr(res["mean"]), _ptr(res["rstd"]),
+                                                       _stream(dev)))
+        return res
+
+    def bn2d_backward(self, x, gamma, beta, mean, rstd, dy, relu=True, training=True, want=(True, True, True)):
+        """The backward of bn2d_forward_train from dy (B,C,H,W), with the forward's x, mean and rstd: the ReLU mask is recomputed, y is not
+        an input.  Returns dict with dx (B,C,H,W), dgamma and dbeta (C) (overwritten, not accumulated), each only where `want` = (dx,
+        dgamma, dbeta) asks for it; a gradient's bits do not depend on which others are formed.  No host synchronisation."""
+        dev = self.device
+        B, C, HW = self._bn2d_args("bn2d_backward", x, ((gamma, "gamma"), (beta, "beta"), (mean, "mean"), (rstd, "rstd")), dy)
+        if gamma is None or beta is None or mean is None or rstd is None or dy is None:
+            raise ImxError("bn2d_backward: gamma, beta, mean, rstd and dy are required")
+        if len(want) != 3:
+            raise ImxError(f"bn2d_backward: want must be three flags (dx, dgamma, dbeta), got {want!r}")
+        res = {}
+        for name, wanted, shape in (("dx", want[0], tuple(x.shape)), ("dgamma", want[1], (C,)), ("dbeta", want[2], (C,))):
+            if wanted:
+                res[name] = torch.empty(shape, dtype=torch.float32, device=dev)
+        self._check(self.spnorm.imx_bn2d_backward(self.handle, B, C, HW, 1 if relu else 0, 1 if training else 0, _ptr(x), _ptr(gamma), _ptr(beta),
+                                                  _ptr(mean), _ptr(rstd), _ptr(dy), _ptr(res.get("dx")), _ptr(res.get("dgamma")),
+                                                  _ptr(res.get("dbeta")), _stream(dev)))
         return res
 
     # ------------------------------------------------------------------ kernel-form options (include/imx.h: imx_set_option)
