@@ -304,7 +304,9 @@ def test_tile_pair_winograd_form_is_bit_identical_to_the_tile_per_workgroup_form
     number of tiles at the second level: the last pair has a dead tile); ragged 123x165 (partial tiles, masked stores).
     Between two pair-form layers without a pool between them (conv2a -> conv2b, ...) the tensor is TILE-SWIZZLED (the accumulators' own
     lane order, 1 KB per store instruction; whole padded tiles, the consumer zeroes what lies outside the image): pure data movement, so
-    the same bits again -- also against "conv_swizzle" = "off", which keeps the pixel-major blocked layout."""
+    the same bits again -- also against "conv_swizzle" = "off", which keeps the pixel-major blocked layout.
+    These three shapes never run conv4a / conv4b as a pair and reach few of the FASTW variants: tests/test_gpu_superpoint_tiles.py holds
+    the pair form to the tile form on every tap at shapes that do."""
     from image_matching_amd import _lib as L
     from image_matching_amd.engine import Engine
     d = 128
