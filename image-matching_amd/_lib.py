@@ -1,5 +1,5 @@
 """ctypes binding of libimx.so (C ABI: include/imx.h), libimx_train.so (include/imx_train.h), libimx_sgtrain.so
-(include/imx_sgtrain.h), libimx_spnet.so (include/imx_spnet.h) and libimx_spnorm.so (include/imx_spnorm.h).  There is no CPU fallback: if the library is missing or no GPU is present the product path raises."""
+(include/imx_sgtrain.h), libimx_spnet.so (include/imx_spnet.h), libimx_spnorm.so (include/imx_spnorm.h) and libimx_sppool.so (include/imx_sppool.h).  There is no CPU fallback: if the library is missing or no GPU is present the product path raises."""
 import ctypes
 import os
 
@@ -91,11 +91,23 @@ _SPNORM_ARGTYPES = {
 }
 SPNORM_EXPORTS = tuple(_SPNORM_ARGTYPES)
 
+# libimx_sppool.so (C ABI: include/imx_sppool.h): MaxPool2d(2) and the descriptor normalisation of SuperPoint's training step on NCHW maps, on
+# libimx.so's handles -- a library of its own because the other five symbol tables are pinned to their headers; name -> argtypes
+SPPOOL_LIB_PATH = os.path.join(_HERE, "libimx_sppool.so")
+_SPPOOL_ARGTYPES = {
+    "imx_maxpool2_forward_train": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
+    "imx_maxpool2_backward": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
+    "imx_l2norm_forward_train": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
+    "imx_l2norm_backward": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
+}
+SPPOOL_EXPORTS = tuple(_SPPOOL_ARGTYPES)
+
 _lib = None
 _train = None
 _sgtrain = None
 _spnet = None
 _spnorm = None
+_sppool = None
 
 
 def load_library():
@@ -217,4 +229,19 @@ def load_spnorm_library():
     for name, argtypes in _SPNORM_ARGTYPES.items():
         getattr(lib, name).argtypes = argtypes          # raises AttributeError if a declared symbol is missing
     _spnorm = lib
+    return lib
+
+
+def load_sppool_library():
+    """Load libimx_sppool.so (built beside libimx.so by the same make); libimx.so is loaded first: it makes the handles."""
+    global _sppool
+    if _sppool is not None:
+        return _sppool
+    load_library()
+    if not os.path.exists(SPPOOL_LIB_PATH):
+        raise RuntimeError(f"libimx_sppool.so not found at {SPPOOL_LIB_PATH}: build it with `make -C image-matching_amd/csrc`")
+    lib = ctypes.CDLL(SPPOOL_LIB_PATH)
+    for name, argtypes in _SPPOOL_ARGTYPES.items():
+        getattr(lib, name).argtypes = argtypes          # raises AttributeError if a declared symbol is missing
+    _sppool = lib
     return lib

@@ -47,6 +47,7 @@ class Engine:
         self.sgtrain = L.load_sgtrain_library()    # the score product of SuperGlue's training step (include/imx_sgtrain.h), likewise
         self.spnet = L.load_spnet_library()        # the 3x3 convolutions of SuperPoint's training step (include/imx_spnet.h), likewise
         self.spnorm = L.load_spnorm_library()      # BatchNorm2d [+ ReLU] of SuperPoint's training step (include/imx_spnorm.h), likewise
+        self.sppool = L.load_sppool_library()      # MaxPool2d(2) and the descriptor normalisation of that step (include/imx_sppool.h), likewise
         if not torch.cuda.is_available():
             raise ImxError("image_matching_amd needs a ROCm GPU (torch.cuda.is_available() is False); "
                            "there is no CPU fallback on the product path")
@@ -1087,6 +1088,72 @@ class Engine:
                                                   _ptr(mean), _ptr(rstd), _ptr(dy), _ptr(res.get("dx")), _ptr(res.get("dgamma")),
                                                   _ptr(res.get("dbeta")), _stream(dev)))
         return res
+
+    # ------------------------------------------------------------------ MaxPool2d(2) and desc / ||desc||_2, training form (include/imx_sppool.h)
+    @staticmethod
+    def _sppool_tensor(who, t, what, dtype=torch.float32):
+        """t is a contiguous cuda tensor of `dtype`, otherwise ImxError (no silent copy)"""
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != dtype or not t.is_contiguous():
+            raise ImxError(f"{who}: {what} must be a contiguous {str(dtype).replace('torch.', '')} cuda tensor")
+
+    def maxpool2_forward_train(self, x, want_idx=True):
+        """F.max_pool2d(x, 2) on x (B,C,H,W), NCHW in place: kernel 2, stride 2, no padding, floor.  Returns dict: y (B,C,H//2,W//2) and
+        idx, a torch.uint8 tensor of y's shape holding 2 row + col of each window's maximum (PyTorch's tie and NaN rule), what
+        maxpool2_backward needs; idx is None with want_idx=False (evaluation), y has the same bits.  No host synchronisation."""
+        who = "maxpool2_forward_train"
+        self._sppool_tensor(who, x, "x")
+        if x.dim() != 4:
+            raise ImxError(f"{who}: x must be (B,C,H,W), got {tuple(x.shape)}")
+        B, C, H, W = (int(s) for s in x.shape)
+        y = torch.empty((B, C, H // 2, W // 2), dtype=torch.float32, device=x.device)
+        idx = torch.empty((B, C, H // 2, W // 2), dtype=torch.uint8, device=x.device) if want_idx else None
+        self._check(self.sppool.imx_maxpool2_forward_train(self.handle, B, C, H, W, _ptr(x), _ptr(y), _ptr(idx), _stream(self.device)))
+        return {"y": y, "idx": idx}
+
+    def maxpool2_backward(self, idx, dy, shape):
+        """The backward of maxpool2_forward_train for an input of `shape` = (B,C,H,W): dx holds dy (B,C,H//2,W//2) at the element idx
+        recorded for each window and +0 everywhere else, written in full.  Returns dict: dx.  No host synchronisation."""
+        who = "maxpool2_backward"
+        self._sppool_tensor(who, idx, "idx", torch.uint8)
+        self._sppool_tensor(who, dy, "dy")
+        if len(shape) != 4:
+            raise ImxError(f"{who}: shape must be (B,C,H,W), got {tuple(shape)}")
+        B, C, H, W = (int(s) for s in shape)
+        for t, what in ((idx, "idx"), (dy, "dy")):
+            if tuple(t.shape) != (B, C, H // 2, W // 2):
+                raise ImxError(f"{who}: {what} must be ({B},{C},{H // 2},{W // 2}), got {tuple(t.shape)}")
+        dx = torch.empty((B, C, H, W), dtype=torch.float32, device=dy.device)
+        self._check(self.sppool.imx_maxpool2_backward(self.handle, B, C, H, W, _ptr(idx), _ptr(dy), _ptr(dx), _stream(self.device)))
+        return {"dx": dx}
+
+    def l2norm_forward_train(self, x):
+        """x / torch.norm(x, p=2, dim=1, keepdim=True) on x (B,C,H,W) or (B,C,N): a true division, no epsilon (a zero vector gives NaN
+        in its own pixel).  Returns dict: y of x's shape and norm (B,H,W) or (B,N), what l2norm_backward needs.  No host synchronisation."""
+        who = "l2norm_forward_train"
+        self._sppool_tensor(who, x, "x")
+        if x.dim() not in (3, 4):
+            raise ImxError(f"{who}: x must be (B,C,H,W) or (B,C,N), got {tuple(x.shape)}")
+        B, C = int(x.shape[0]), int(x.shape[1])
+        HW = x.numel() // max(B * C, 1)
+        res = {"y": torch.empty_like(x), "norm": torch.empty((B,) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)}
+        self._check(self.sppool.imx_l2norm_forward_train(self.handle, B, C, HW, _ptr(x), _ptr(res["y"]), _ptr(res["norm"]), _stream(self.device)))
+        return res
+
+    def l2norm_backward(self, y, norm, dy):
+        """The backward of l2norm_forward_train from dy of y's shape, with the forward's y and norm: dx = (dy - y sum_c(y dy)) / norm.
+        Returns dict: dx.  No host synchronisation."""
+        who = "l2norm_backward"
+        for t, what in ((y, "y"), (norm, "norm"), (dy, "dy")):
+            self._sppool_tensor(who, t, what)
+        if y.dim() not in (3, 4):
+            raise ImxError(f"{who}: y must be (B,C,H,W) or (B,C,N), got {tuple(y.shape)}")
+        if dy.shape != y.shape or tuple(norm.shape) != (int(y.shape[0]),) + tuple(y.shape[2:]):
+            raise ImxError(f"{who}: dy must be {tuple(y.shape)} and norm {(int(y.shape[0]),) + tuple(y.shape[2:])}, got {tuple(dy.shape)} and {tuple(norm.shape)}")
+        B, C = int(y.shape[0]), int(y.shape[1])
+        HW = y.numel() // max(B * C, 1)
+        dx = torch.empty_like(y)
+        self._check(self.sppool.imx_l2norm_backward(self.handle, B, C, HW, _ptr(y), _ptr(norm), _ptr(dy), _ptr(dx), _stream(self.device)))
+        return {"dx": dx}
 
     # ------------------------------------------------------------------ kernel-form options (include/imx.h: imx_set_option)
     def set_option(self, key, value):

@@ -1,7 +1,8 @@
 """SuperPoint's own layers in their training form, with `loss.backward()` running through the project's kernels: the 3x3 convolutions
-of libimx_spnet (include/imx_spnet.h, csrc/conv3_train.hip) and the BatchNorm2d [+ ReLU] of libimx_spnorm
-(include/imx_spnorm.h, csrc/bn2d_train.hip; section 19) as torch.autograd.Functions, and on them the reference's `double_conv` and `down`
-blocks (superpoint/models/unet_parts.py:10-48) and the two-layer heads of its network (superpoint/models/superpoint_train.py:47-51).
+of libimx_spnet (include/imx_spnet.h, csrc/conv3_train.hip), the BatchNorm2d [+ ReLU] of libimx_spnorm
+(include/imx_spnorm.h, csrc/bn2d_train.hip; section 19) and the max-pooling and descriptor normalisation of libimx_sppool
+(include/imx_sppool.h, csrc/sppool_train.hip; section 20) as torch.autograd.Functions, and on them the reference's `double_conv` and `down`
+blocks (superpoint/models/unet_parts.py:10-48) and the two-layer heads of its network (superpoint/models/superpoint_train.py:47-54).
 
     conv3x3.apply(engine, x, weight, bias)      F.conv2d(x, weight, bias, padding=1) for a (Cout,Cin,3,3) weight
     conv2d(engine, x, weight, bias)             the same, as a function
@@ -12,12 +13,17 @@ blocks (superpoint/models/unet_parts.py:10-48) and the two-layer heads of its ne
     down(engine, block, x)                      block(x) for the reference's down (nn.MaxPool2d(2) stays F.max_pool2d)
     conv_bn_relu_form / double_conv_form / down_form (..., form="auto")    the same three with the BatchNorm form chosen by the caller
     head(engine, conv_a, bn_a, conv_b, bn_b, x) bn_b(conv_b(relu(bn_a(conv_a(x))))), conv_a 3x3 and conv_b 1x1
+    maxpool2.apply(engine, x)                   F.max_pool2d(x, 2); saved for the backward: one index byte per output
+    max_pool2(engine, x)                        the same, as a function
+    l2norm.apply(engine, x)                     x / torch.norm(x, p=2, dim=1, keepdim=True); saved: the output and the norms
+    normalize_descriptors(engine, x)            the same, as a function
+    down_pooled(engine, block, x, form="auto")  down_form with the max-pooling on libimx_sppool's kernels
 
 Tensors are the reference's own, NCHW contiguous fp32 on the engine's device; nothing is copied to another layout.  BatchNorm + ReLU has
 two forms.  "channel": the kernels of libimx_train (sgtrain_grad.bn_relu) on the (B, C, H W) view, one workgroup per channel, bound to
 H W <= 2^20.  "pixels": libimx_spnorm's, the work split over slabs of 4096 pixels, H W <= 2^24 and B H W < 2^31.  "auto" chooses by
-pixels_form(B, C, H W), a rule on the shape alone.  conv2d alone serves H, W <= 4096.  Max-pooling on the project's kernels, the
-descriptor normalisation and a trainable SuperPointNet are not here."""
+pixels_form(B, C, H W), a rule on the shape alone.  conv2d alone serves H, W <= 4096.  down / down_form keep F.max_pool2d; down_pooled
+pools through max_pool2.  The network assembled from these with live parameters is sptrain_model.SuperPointTrainable."""
 import torch
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
@@ -211,3 +217,88 @@ def head(engine, conv_a, bn_a, conv_b, bn_b, x):
     if cancels:
         z = _bias_before_batchnorm.apply(z, bias)
     return batchnorm2d(engine, bn_b, z.view(B, conv_b.out_channels, H, W), relu=False)
+
+
+class maxpool2(torch.autograd.Function):
+    """maxpool2.apply(engine, x): F.max_pool2d(x, 2) on x (B,C,H,W) -- kernel 2, stride 2, no padding, floor -- with PyTorch's tie and
+    NaN rule, differentiable with respect to x.  Saved for the backward: idx only, one byte per output; neither x nor y."""
+
+    @staticmethod
+    def forward(ctx, engine, x):
+        _require(x, "maxpool2: x")
+        res = engine.maxpool2_forward_train(x, want_idx=bool(ctx.needs_input_grad[1]))
+        ctx.engine, ctx.shape = engine, tuple(x.shape)
+        if res["idx"] is not None:
+            ctx.save_for_backward(res["idx"])
+        return res["y"]
+
+    @staticmethod
+    @once_differentiable                                                 # the kernels form first derivatives only
+    def backward(ctx, grad_y):
+        if not ctx.needs_input_grad[1]:
+            return None, None
+        idx, = ctx.saved_tensors
+        grad_y = grad_y.contiguous()                                     # (autograd's own tensor: it may hand over a view)
+        _require(grad_y, "maxpool2: grad_y")
+        return None, ctx.engine.maxpool2_backward(idx, grad_y, ctx.shape)["dx"]
+
+
+def max_pool2(engine, x):
+    """F.max_pool2d(x, 2), what nn.MaxPool2d(2) computes, through libimx_sppool's kernels; an input that needs no gradient records no
+    indices."""
+    return maxpool2.apply(engine, x)
+
+
+class l2norm(torch.autograd.Function):
+    """l2norm.apply(engine, x): x / torch.norm(x, p=2, dim=1, keepdim=True) on x (B,C,H,W) or (B,C,N), a true division without epsilon
+    (superpoint_train.py:53-54), differentiable with respect to x.  Saved for the backward: y and norm; not x."""
+
+    @staticmethod
+    def forward(ctx, engine, x):
+        _require(x, "l2norm: x")
+        res = engine.l2norm_forward_train(x)
+        ctx.engine = engine
+        ctx.save_for_backward(res["y"], res["norm"])
+        return res["y"]
+
+    @staticmethod
+    @once_differentiable                                                 # the kernels form first derivatives only
+    def backward(ctx, grad_y):
+        if not ctx.needs_input_grad[1]:
+            return None, None
+        y, norm = ctx.saved_tensors
+        grad_y = grad_y.contiguous()                                     # (autograd's own tensor: it may hand over a view)
+        _require(grad_y, "l2norm: grad_y")
+        return None, ctx.engine.l2norm_backward(y, norm, grad_y)["dx"]
+
+
+def normalize_descriptors(engine, x):
+    """desc.div(torch.unsqueeze(torch.norm(desc, p=2, dim=1), 1)) (superpoint_train.py:53-54) through libimx_sppool's kernels"""
+    return l2norm.apply(engine, x)
+
+
+def _double_conv_layers(block):
+    """the six modules of the reference's double_conv, or ImxError.  A COPY of the layout check inside double_conv_form, for a caller that
+    has work to do before that function runs: whoever changes one changes the other (double_conv_form keeps its own because this
+    change only adds to the module; having it call this helper is the tidy form)"""
+    seq = getattr(block, "conv", None)
+    mods = list(seq) if isinstance(seq, torch.nn.Sequential) else []
+    if len(mods) != 6 or not all(_is_conv3(m) for m in mods[0::3]) or not all(isinstance(m, torch.nn.BatchNorm2d) for m in mods[1::3]) \
+            or not all(isinstance(m, torch.nn.ReLU) for m in mods[2::3]):
+        raise ImxError("double_conv: expected .conv = Sequential(Conv2d(3, padding=1), BatchNorm2d, ReLU, Conv2d(3, padding=1), BatchNorm2d, ReLU), got "
+                       + (" ".join(type(m).__name__ for m in mods) if mods else type(block).__name__))
+    return mods
+
+
+def down_pooled(engine, block, x, form="auto"):
+    """down_form(engine, block, x, form) with the max-pooling through max_pool2 instead of F.max_pool2d: block(x) for the reference's
+    down (unet_parts.py:38-48), block.mpconv = Sequential(MaxPool2d(2), double_conv).  Any other layout raises ImxError."""
+    seq = getattr(block, "mpconv", None)
+    mods = list(seq) if isinstance(seq, torch.nn.Sequential) else []
+    if len(mods) != 2 or not isinstance(mods[0], torch.nn.MaxPool2d) or mods[0].kernel_size not in (2, (2, 2)) \
+            or mods[0].stride not in (2, (2, 2)) or mods[0].padding not in (0, (0, 0)) or mods[0].dilation not in (1, (1, 1)) \
+            or mods[0].ceil_mode or mods[0].return_indices:
+        raise ImxError("down: expected .mpconv = Sequential(MaxPool2d(2), double_conv), got "
+                       + (" ".join(type(m).__name__ for m in mods) if mods else type(block).__name__))
+    _double_conv_layers(mods[1])                                         # (a layout error before anything runs)
+    return double_conv_form(engine, mods[1], max_pool2(engine, x), form)
