@@ -1,5 +1,6 @@
 """ctypes binding of libimx.so (C ABI: include/imx.h), libimx_train.so (include/imx_train.h), libimx_sgtrain.so
-(include/imx_sgtrain.h), libimx_spnet.so (include/imx_spnet.h), libimx_spnorm.so (include/imx_spnorm.h) and libimx_sppool.so (include/imx_sppool.h).  There is no CPU fallback: if the library is missing or no GPU is present the product path raises."""
+(include/imx_sgtrain.h), libimx_spnet.so (include/imx_spnet.h), libimx_spnorm.so (include/imx_spnorm.h), libimx_sppool.so (include/imx_sppool.h)
+and libimx_photo.so (include/imx_photo.h).  There is no CPU fallback: if the library is missing or no GPU is present the product path raises."""
 import ctypes
 import os
 
@@ -102,12 +103,22 @@ _SPPOOL_ARGTYPES = {
 }
 SPPOOL_EXPORTS = tuple(_SPPOOL_ARGTYPES)
 
+# libimx_photo.so (C ABI: include/imx_photo.h): the photometric augmentation of SuperPoint's training data, on libimx.so's handles -- a library
+# of its own because the other six symbol tables are pinned to their headers; name -> argtypes
+PHOTO_LIB_PATH = os.path.join(_HERE, "libimx_photo.so")
+_PHOTO_ARGTYPES = {
+    "imx_photo_pixels": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "imx_photo_shade": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+}
+PHOTO_EXPORTS = tuple(_PHOTO_ARGTYPES)
+
 _lib = None
 _train = None
 _sgtrain = None
 _spnet = None
 _spnorm = None
 _sppool = None
+_photo = None
 
 
 def load_library():
@@ -244,4 +255,19 @@ def load_sppool_library():
     for name, argtypes in _SPPOOL_ARGTYPES.items():
         getattr(lib, name).argtypes = argtypes          # raises AttributeError if a declared symbol is missing
     _sppool = lib
+    return lib
+
+
+def load_photo_library():
+    """Load libimx_photo.so (built beside libimx.so by the same make); libimx.so is loaded first: it makes the handles."""
+    global _photo
+    if _photo is not None:
+        return _photo
+    load_library()
+    if not os.path.exists(PHOTO_LIB_PATH):
+        raise RuntimeError(f"libimx_photo.so not found at {PHOTO_LIB_PATH}: build it with `make -C image-matching_amd/csrc`")
+    lib = ctypes.CDLL(PHOTO_LIB_PATH)
+    for name, argtypes in _PHOTO_ARGTYPES.items():
+        getattr(lib, name).argtypes = argtypes          # raises AttributeError if a declared symbol is missing
+    _photo = lib
     return lib

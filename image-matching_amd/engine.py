@@ -48,6 +48,7 @@ class Engine:
         self.spnet = L.load_spnet_library()        # the 3x3 convolutions of SuperPoint's training step (include/imx_spnet.h), likewise
         self.spnorm = L.load_spnorm_library()      # BatchNorm2d [+ ReLU] of SuperPoint's training step (include/imx_spnorm.h), likewise
         self.sppool = L.load_sppool_library()      # MaxPool2d(2) and the descriptor normalisation of that step (include/imx_sppool.h), likewise
+        self.photo = L.load_photo_library()        # the photometric augmentation of that step's data (include/imx_photo.h), likewise
         if not torch.cuda.is_available():
             raise ImxError("image_matching_amd needs a ROCm GPU (torch.cuda.is_available() is False); "
                            "there is no CPU fallback on the product path")
@@ -1154,6 +1155,73 @@ class Engine:
         dx = torch.empty_like(y)
         self._check(self.sppool.imx_l2norm_backward(self.handle, B, C, HW, _ptr(y), _ptr(norm), _ptr(dy), _ptr(dx), _stream(self.device)))
         return {"dx": dx}
+
+    # ------------------------------------------------------------------ photometric augmentation (include/imx_photo.h)
+    def _photo_tensor(self, who, t, what, dtype, shape):
+        """t is a contiguous cuda tensor of `dtype` and `shape`, otherwise ImxError (no silent copy)"""
+        self._sppool_tensor(who, t, what, dtype)
+        if tuple(t.shape) != tuple(shape):
+            raise ImxError(f"{who}: {what} must be {tuple(shape)}, got {tuple(t.shape)}")
+
+    def photo_pixels(self, images, lut, noise_scale, thresh, table, blur_kernel, blur_on, key):
+        """imx_photo_pixels on images (B,H,W) float32 in [0,1]: the per-image table lut (B,256) uint8, Gaussian noise of noise_scale (B),
+        impulse noise below thresh (B) from table (256) uint8, the 3x3 correlation blur_kernel (B,9) where blur_on (B) is set; per-pixel
+        draws from Philox4x32-10 under key (B,2).  thresh, blur_on and key are int32 tensors (key and thresh hold uint32 bit patterns).
+        Returns (B,H,W) uint8.  No host synchronisation."""
+        who = "photo_pixels"
+        self._sppool_tensor(who, images, "images")
+        if images.dim() != 3:
+            raise ImxError(f"{who}: images must be (B,H,W), got {tuple(images.shape)}")
+        B, H, W = (int(s) for s in images.shape)
+        i32, u8, f32 = torch.int32, torch.uint8, torch.float32
+        for t, what, dt, shape in ((lut, "lut", u8, (B, 256)), (noise_scale, "noise_scale", f32, (B,)), (thresh, "thresh", i32, (B,)),
+                                   (table, "table", u8, (256,)), (blur_kernel, "blur_kernel", f32, (B, 9)), (blur_on, "blur_on", i32, (B,)),
+                                   (key, "key", i32, (B, 2))):
+            self._photo_tensor(who, t, what, dt, shape)
+        out = torch.empty((B, H, W), dtype=u8, device=images.device)
+        self._check(self.photo.imx_photo_pixels(self.handle, B, H, W, _ptr(images), _ptr(lut), _ptr(noise_scale), _ptr(thresh), _ptr(table),
+                                                _ptr(blur_kernel), _ptr(blur_on), _ptr(key), _ptr(out), _stream(self.device)))
+        return out
+
+    def photo_shade(self, images_u8, ellipses, n_ellipses, taps, ksize, transparency, on):
+        """imx_photo_shade on images_u8 (B,H,W) uint8: the union of ellipses (B,E,5) = (cx, cy, ax, ay, degrees), the first n_ellipses (B)
+        int32 of each image, blurred with the Gaussian taps (B,Kcap) of which image b uses ksize[b] -- a HOST sequence of B odd
+        integers in 3..Kcap, read during the call -- and applied with transparency (B); on (B) int32 clear leaves the image / 255.
+        Returns (B,H,W) float32.  No host synchronisation."""
+        who = "photo_shade"
+        self._sppool_tensor(who, images_u8, "images_u8", torch.uint8)
+        if images_u8.dim() != 3 or ellipses.dim() != 3 or taps.dim() != 2:
+            raise ImxError(f"{who}: images_u8 must be (B,H,W), ellipses (B,E,5) and taps (B,Kcap)")
+        B, H, W = (int(s) for s in images_u8.shape)
+        E, Kcap = int(ellipses.shape[1]), int(taps.shape[1])
+        i32, f32 = torch.int32, torch.float32
+        for t, what, dt, shape in ((ellipses, "ellipses", f32, (B, E, 5)), (n_ellipses, "n_ellipses", i32, (B,)), (taps, "taps", f32, (B, Kcap)),
+                                   (transparency, "transparency", f32, (B,)), (on, "on", i32, (B,))):
+            self._photo_tensor(who, t, what, dt, shape)
+        ks = np.ascontiguousarray(np.asarray(ksize, dtype=np.int32).reshape(-1))
+        if ks.size != B:
+            raise ImxError(f"{who}: ksize must hold {B} integers on the host, got {ks.size}")
+        out = torch.empty((B, H, W), dtype=f32, device=images_u8.device)
+        self._check(self.photo.imx_photo_shade(self.handle, B, H, W, E, Kcap, _ptr(images_u8), _ptr(ellipses), _ptr(n_ellipses), _ptr(taps),
+                                               ks.ctypes.data_as(ctypes.c_void_p), _ptr(transparency), _ptr(on), _ptr(out), _stream(self.device)))
+        return out
+
+    def photometric(self, images, params):
+        """The reference's imgPhotometric (datasets/ALLSS.py:116-128) for a batch: images (B,1,H,W) or (B,H,W) float32 in [0,1], params the
+        dict of host arrays photometric.sample_params drew (one entry per image).  Both calls on the current stream; returns float32
+        (B,1,H,W).  No host synchronisation."""
+        who = "photometric"
+        x = images[:, 0] if images.dim() == 4 else images
+        self._sppool_tensor(who, x, "images")
+        dev = x.device
+
+        def up(name, as_i32=False):
+            a = np.ascontiguousarray(params[name])
+            return torch.from_numpy(a.view(np.int32) if as_i32 else a).to(dev)
+        u8 = self.photo_pixels(x, up("lut"), up("noise_scale"), up("thresh", True), up("table"), up("blur_kernel"), up("blur_on"),
+                               up("key", True))
+        out = self.photo_shade(u8, up("ellipses"), up("n_ellipses"), up("taps"), params["ksize"], up("transparency"), up("shade_on"))
+        return out[:, None]
 
     # ------------------------------------------------------------------ kernel-form options (include/imx.h: imx_set_option)
     def set_option(self, key, value):

@@ -5,6 +5,9 @@ N synthetic images whose pseudo-labels come from homographic adaptation (export_
 
     python superpoint_validate_descriptor.py --synthetic 2 --size 120 160
 
+--photometric runs the pass on the training split's data path instead: `augmentation.photometric` (the shipped yaml's settings, or the
+--config file's) applied to both images of every pair on the GPU (datasets/ALLSS_photo.py, include/imx_photo.h).
+
 --grads prints the norms of the loss gradients at the network's outputs as well (include/imx_train.h).  The backward of the network's
 own layers is not here: training itself stays with the reference, which may take those cotangents."""
 import argparse
@@ -24,6 +27,13 @@ SHIPPED = {  # superpoint/configs/superpoint_allss_train_heatmap.yaml without th
               'sparse_loss': {'enable': True, 'params': {'num_matching_attempts': 1000, 'num_masked_non_matches_per_match': 100,
                                                          'lamda_d': 1, 'dist': 'cos', 'method': '2d'}}},
 }
+SHIPPED_PHOTOMETRIC = {  # data.augmentation.photometric of the same yaml
+    'enable': True,
+    'primitives': ['random_brightness', 'random_contrast', 'additive_speckle_noise', 'additive_gaussian_noise', 'additive_shade', 'motion_blur'],
+    'params': {'random_brightness': {'max_abs_change': 50}, 'random_contrast': {'strength_range': [0.5, 1.5]},
+               'additive_gaussian_noise': {'stddev_range': [0, 10]}, 'additive_speckle_noise': {'prob_range': [0, 0.0035]},
+               'additive_shade': {'transparency_range': [-0.5, 0.5], 'kernel_size_range': [100, 150]}, 'motion_blur': {'max_kernel_size': 3}},
+}
 
 if __name__ == '__main__':
     parser = argparse.ArgumentParser()
@@ -34,11 +44,14 @@ if __name__ == '__main__':
     parser.add_argument("--size", type=int, nargs=2, default=None, help="H W of the synthetic images (default: preprocessing.resize)")
     parser.add_argument("--grads", action="store_true",
                         help="run the losses as value-and-gradient calls and print the L2 norms of d loss / d semi, semi_warp, desc, desc_warp too")
+    parser.add_argument("--photometric", action="store_true",
+                        help="augment both images of every pair photometrically on the GPU, as the training split does (task='train')")
     args = parser.parse_args()
 
     from image_matching_amd import homoadapt, synth
     from image_matching_amd import _lib as L
     from image_matching_amd.datasets.ALLSS import ALLSS
+    from image_matching_amd.datasets.ALLSS_photo import ALLSSPhotometric
     from image_matching_amd.superpoint.Train_model_heatmap import Train_model_heatmap
 
     config = SHIPPED
@@ -46,12 +59,16 @@ if __name__ == '__main__':
         import yaml
         with open(args.config, 'r') as f:
             config = yaml.safe_load(f)
-        for key in ('photometric',):
-            config['data'].get('augmentation', {}).get(key, {})['enable'] = False      # imgaug steps: not served, said so in the README
+        if not args.photometric:
+            config['data'].get('augmentation', {}).get('photometric', {})['enable'] = False
         config['data'].get('gaussian_label', {})['enable'] = False
     agent = Train_model_heatmap(config, device='cuda')
     agent.loadModel()
     data_cfg = {k: v for k, v in config['data'].items() if k not in ('dataset', 'root', 'root_split_txt')}
+    make_set, task = ALLSS, 'val'
+    if args.photometric:
+        make_set, task = ALLSSPhotometric, 'train'
+        data_cfg.setdefault('augmentation', {}).setdefault('photometric', SHIPPED_PHOTOMETRIC)
     if args.synthetic:
         H, W = args.size or config['data']['preprocessing']['resize']
         eng = agent.net._shared.get_engine([L.NET_SUPERPOINT])
@@ -59,9 +76,9 @@ if __name__ == '__main__':
         hom, inv = homoadapt.sample_homographies(16, 0, **homoadapt.EXPORT_PARAMS)
         points = [homoadapt.export_image(eng, torch.from_numpy(im).to(eng.device), hom, inv, config['model']['detection_threshold'],
                                          config['model']['nms'], top_k=600) for im in images]
-        val_set = ALLSS(task='val', images=images, points=points, **data_cfg)
+        val_set = make_set(task=task, images=images, points=points, **data_cfg)
     else:
-        val_set = ALLSS(task='val', **data_cfg)
+        val_set = make_set(task=task, **data_cfg)
     bs = config['model']['eval_batch_size']
     totals, batches = {}, 0
     for i0 in range(0, len(val_set), bs):
