@@ -1,6 +1,6 @@
 """ctypes binding of libimx.so (C ABI: include/imx.h), libimx_train.so (include/imx_train.h), libimx_sgtrain.so
-(include/imx_sgtrain.h), libimx_spnet.so (include/imx_spnet.h), libimx_spnorm.so (include/imx_spnorm.h), libimx_sppool.so (include/imx_sppool.h)
-and libimx_photo.so (include/imx_photo.h).  There is no CPU fallback: if the library is missing or no GPU is present the product path raises."""
+(include/imx_sgtrain.h), libimx_spnet.so (include/imx_spnet.h), libimx_spnorm.so (include/imx_spnorm.h), libimx_sppool.so (include/imx_sppool.h),
+libimx_photo.so (include/imx_photo.h) and libimx_sploop.so (include/imx_sploop.h).  There is no CPU fallback: if the library is missing or no GPU is present the product path raises."""
 import ctypes
 import os
 
@@ -112,6 +112,16 @@ _PHOTO_ARGTYPES = {
 }
 PHOTO_EXPORTS = tuple(_PHOTO_ARGTYPES)
 
+# libimx_sploop.so (C ABI: include/imx_sploop.h): the bilinear label splat of gaussian_label and the flat Adam step of SuperPoint's training
+# loop, on libimx.so's handles -- a library of its own because the other seven symbol tables are pinned to their headers; name -> argtypes
+SPLOOP_LIB_PATH = os.path.join(_HERE, "libimx_sploop.so")
+_f64, _i64 = ctypes.c_double, ctypes.c_int64
+_SPLOOP_ARGTYPES = {
+    "imx_warp_labels_bi": [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
+    "imx_adam_flat": [_vp, _vp, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _f64, _f64, _i32, _vp],
+}
+SPLOOP_EXPORTS = tuple(_SPLOOP_ARGTYPES)
+
 _lib = None
 _train = None
 _sgtrain = None
@@ -119,6 +129,7 @@ _spnet = None
 _spnorm = None
 _sppool = None
 _photo = None
+_sploop = None
 
 
 def load_library():
@@ -270,4 +281,19 @@ def load_photo_library():
     for name, argtypes in _PHOTO_ARGTYPES.items():
         getattr(lib, name).argtypes = argtypes          # raises AttributeError if a declared symbol is missing
     _photo = lib
+    return lib
+
+
+def load_sploop_library():
+    """Load libimx_sploop.so (built beside libimx.so by the same make); libimx.so is loaded first: it makes the handles."""
+    global _sploop
+    if _sploop is not None:
+        return _sploop
+    load_library()
+    if not os.path.exists(SPLOOP_LIB_PATH):
+        raise RuntimeError(f"libimx_sploop.so not found at {SPLOOP_LIB_PATH}: build it with `make -C image-matching_amd/csrc`")
+    lib = ctypes.CDLL(SPLOOP_LIB_PATH)
+    for name, argtypes in _SPLOOP_ARGTYPES.items():
+        getattr(lib, name).argtypes = argtypes          # raises AttributeError if a declared symbol is missing
+    _sploop = lib
     return lib

@@ -24,13 +24,7 @@ namespace {
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
-// One row of warp_points' matrix product H @ (x, y, 1) (utils/utils.py:561-584) as torch's CPU product evaluates it on a processor
-// with fused multiply-add: k ascending, the first product rounded, every later term fused into the running sum.  The fixtures
-// the reference wrote agree with this order bit for bit (tests/sptrain_ref.py: warp_points).
-__device__ __forceinline__ float warp_row(const float* __restrict__ m, float x, float y) {
-#pragma clang fp contract(off)
-  return fmaf(m[2], 1.0f, fmaf(m[1], y, m[0] * x));
-}
+// (warp_row and warp_point, the matrix product of warp_points, are in sptrain_dev.h: libimx_sploop.so warps by the same function)
 
 // ------------------------------------------------------------------------------------------------------------- warp_labels
 __global__ __launch_bounds__(256) void wl_fill_kernel(WarpLabelsArgs a) {
@@ -58,8 +52,8 @@ __device__ __forceinline__ bool wl_pixel(const WarpLabelsArgs& a, int b, int i, 
     return true;
   }
   const float* m = a.mats + (size_t)b * 9;
-  const float u = warp_row(m, x, y), v = warp_row(m + 3, x, y), w = warp_row(m + 6, x, y);
-  const float wx = u / w, wy = v / w;
+  float wx, wy;
+  warp_point(m, x, y, wx, wy);
   if (!(wx >= 0.0f && wx <= xm && wy >= 0.0f && wy <= ym)) return false;   // filter_points on the unrounded point (NaN: dropped)
   const float rx = rintf(wx), ry = rintf(wy);                          // round(): half to even
   px = (int)rx; py = (int)ry; dx = wx - rx; dy = wy - ry;

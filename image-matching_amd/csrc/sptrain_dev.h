@@ -1,4 +1,5 @@
-// sptrain_dev.h -- device helpers of the sparse descriptor loss that its forward (sptrain.hip) and its gradient (spgrad.hip) share:
+// sptrain_dev.h -- device helpers that kernels of more than one unit share: the warp of a label point (sptrain.hip, sploop.hip) and, of
+// the sparse descriptor loss, what its forward (sptrain.hip) and its gradient (spgrad.hip) share:
 // the bilinear taps of the '2d' method, the lane layout of a descriptor row, the row load, the four-tap sample and the dot product.
 // One definition, so both sides form the same numbers from the same instructions.
 #pragma once
@@ -6,6 +7,22 @@
 
 namespace imx {
 namespace {
+
+// One row of warp_points' matrix product H @ (x, y, 1) (utils/utils.py:561-584) as torch's CPU product evaluates it on a processor
+// with fused multiply-add: k ascending, the first product rounded, every later term fused into the running sum.  The fixtures
+// the reference wrote agree with this order bit for bit (tests/sptrain_ref.py: warp_points).
+__device__ __forceinline__ float warp_row(const float* __restrict__ m, float x, float y) {
+#pragma clang fp contract(off)
+  return fmaf(m[2], 1.0f, fmaf(m[1], y, m[0] * x));
+}
+// warp_points of the integer point (x, y) under the pixel-space matrix m: imx_warp_labels (sptrain.hip) and imx_warp_labels_bi
+// (sploop.hip) both warp by this
+__device__ __forceinline__ void warp_point(const float* __restrict__ m, float x, float y, float& wx, float& wy) {
+#pragma clang fp contract(off)
+  const float u = warp_row(m, x, y), v = warp_row(m + 3, x, y), w = warp_row(m + 6, x, y);
+  wx = u / w;
+  wy = v / w;
+}
 
 // bilinear taps of grid_sample (zero padding, align_corners=True) at normPts(p, size): g = p / size * 2 - 1, then
 // ((g + 1) / 2) (size - 1), as torch forms them

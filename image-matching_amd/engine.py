@@ -1,6 +1,7 @@
 """Host-side engine: one libimx handle per (device, config), weight upload, and tensor-level
 wrappers of the C-ABI entry points.  torch tensors are containers only (data_ptr + stream)."""
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -49,6 +50,7 @@ class Engine:
         self.spnorm = L.load_spnorm_library()      # BatchNorm2d [+ ReLU] of SuperPoint's training step (include/imx_spnorm.h), likewise
         self.sppool = L.load_sppool_library()      # MaxPool2d(2) and the descriptor normalisation of that step (include/imx_sppool.h), likewise
         self.photo = L.load_photo_library()        # the photometric augmentation of that step's data (include/imx_photo.h), likewise
+        self.sploop = L.load_sploop_library()      # the soft labels and the optimiser step of the training loop (include/imx_sploop.h), likewise
         if not torch.cuda.is_available():
             raise ImxError("image_matching_amd needs a ROCm GPU (torch.cuda.is_available() is False); "
                            "there is no CPU fallback on the product path")
@@ -1222,6 +1224,55 @@ class Engine:
                                up("key", True))
         out = self.photo_shade(u8, up("ellipses"), up("n_ellipses"), up("taps"), params["ksize"], up("transparency"), up("shade_on"))
         return out[:, None]
+
+    # ------------------------------------------------------------------ the training loop (include/imx_sploop.h)
+    def warp_labels_bi(self, pts, counts, homographies, H, W, levels=0, pixel_space=False):
+        """get_labels_bi (datasets/data_tools.py:9-34) as warpLabels(..., bilinear=True) calls it, for B images: pts (B,Kcap,2) (x, y),
+        counts (B) int32 or None, homographies (B,3,3) on [-1,1]^2 coordinates (scaled to pixels here as warp_labels does).  levels = 0:
+        the bilinear weights (`warped_labels_bi`); levels = 255: floor(255 w) / 255, the 8-bit round trip of ImgAugTransform.__call__
+        (`warped_labels_gaussian` where the blur is the identity).  Returns (out (B,H,W), flag (1) int32 device word: bit 0 = a weight
+        outside [0,1] (a warped coordinate in (-1,0)), bit 1 = a non-finite warped point, dropped).  Several entries on one pixel: the
+        highest order index k count + i writes.  No host synchronisation."""
+        who = "warp_labels_bi"
+        pts = pts if isinstance(pts, torch.Tensor) else torch.as_tensor(np.asarray(pts, dtype=np.float32))
+        pts = pts.to(self.device, torch.float32).contiguous()
+        if pts.dim() != 3 or pts.shape[2] != 2:
+            raise ImxError(f"{who}: pts must be (B,Kcap,2), got {tuple(pts.shape)}")
+        if int(levels) not in (0, 255):
+            raise ImxError(f"{who}: levels must be 0 or 255, got {levels!r}")
+        B, K = int(pts.shape[0]), int(pts.shape[1])
+        counts = self._counts(counts, B, who)
+        if pixel_space:                  # the matrices already act on pixel coordinates: passed to the kernel as they are
+            mats = self._f32(homographies, (B, 3, 3), f"{who}: homographies")
+        else:
+            mats = self._scaled(homographies, B, float(W), float(H), -1.)
+        out = torch.empty(B, int(H), int(W), dtype=torch.float32, device=self.device)
+        flag = torch.empty(1, dtype=torch.int32, device=self.device)
+        self._check(self.sploop.imx_warp_labels_bi(self.handle, _ptr(pts), _ptr(counts), B, K, _ptr(mats), int(H), int(W), int(levels), _ptr(out),
+                                                   _ptr(flag), _stream(self.device)))
+        return out, flag
+
+    def adam_flat(self, p, g, m, v, lr, betas, eps, weight_decay, step, zero_grad=False):
+        """One step of torch.optim.Adam (amsgrad=False, maximize=False) on four flat fp32 cuda tensors of n floats, IN PLACE, one launch:
+        p parameters, g gradients, m exp_avg, v exp_avg_sq.  `step` is the step count t >= 1 AFTER this step, a host integer: the bias
+        corrections are formed here in double.  zero_grad stores 0 to g after reading it.  1-D contiguous views are taken as they
+        are (no copy); anything else raises.  No host synchronisation."""
+        who = "adam_flat"
+        n = int(p.numel())
+        for t, what in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):
+            self._sppool_tensor(who, t, what)
+            if t.dim() != 1 or int(t.numel()) != n:
+                raise ImxError(f"{who}: {what} must be a flat tensor of {n} floats, got {tuple(t.shape)}")
+        step = int(step)
+        if step < 1:
+            raise ImxError(f"{who}: step must be >= 1, got {step}")
+        b1, b2 = float(betas[0]), float(betas[1])
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ImxError(f"{who}: bad scalar: betas must lie in [0, 1), got {betas!r}")
+        step_size = float(lr) / (1.0 - b1 ** step)
+        inv_sqrt_bc2 = 1.0 / math.sqrt(1.0 - b2 ** step)
+        self._check(self.sploop.imx_adam_flat(self.handle, _ptr(p), _ptr(g), _ptr(m), _ptr(v), n, step_size, b1, b2, inv_sqrt_bc2, float(eps),
+                                              float(weight_decay), int(bool(zero_grad)), _stream(self.device)))
 
     # ------------------------------------------------------------------ kernel-form options (include/imx.h: imx_set_option)
     def set_option(self, key, value):
