@@ -1,6 +1,6 @@
 """ctypes binding of libimx.so (C ABI: include/imx.h), libimx_train.so (include/imx_train.h), libimx_sgtrain.so
 (include/imx_sgtrain.h), libimx_spnet.so (include/imx_spnet.h), libimx_spnorm.so (include/imx_spnorm.h), libimx_sppool.so (include/imx_sppool.h),
-libimx_photo.so (include/imx_photo.h) and libimx_sploop.so (include/imx_sploop.h).  There is no CPU fallback: if the library is missing or no GPU is present the product path raises."""
+libimx_photo.so (include/imx_photo.h), libimx_sploop.so (include/imx_sploop.h) and libimx_sgloop.so (include/imx_sgloop.h).  There is no CPU fallback: if the library is missing or no GPU is present the product path raises."""
 import ctypes
 import os
 
@@ -122,6 +122,16 @@ _SPLOOP_ARGTYPES = {
 }
 SPLOOP_EXPORTS = tuple(_SPLOOP_ARGTYPES)
 
+# libimx_sgloop.so (C ABI: include/imx_sgloop.h): the matches of SuperGlue's training forward from the loss's own Sinkhorn, on libimx.so's
+# handles -- a library of its own because the other eight symbol tables are pinned to their headers; name -> argtypes
+SGLOOP_LIB_PATH = os.path.join(_HERE, "libimx_sgloop.so")
+_SGLOOP_ARGTYPES = {
+    "imx_assignment_matches": [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "imx_ot_match_loss_grad_matches": [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp,
+                                       _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+}
+SGLOOP_EXPORTS = tuple(_SGLOOP_ARGTYPES)
+
 _lib = None
 _train = None
 _sgtrain = None
@@ -130,6 +140,7 @@ _spnorm = None
 _sppool = None
 _photo = None
 _sploop = None
+_sgloop = None
 
 
 def load_library():
@@ -296,4 +307,19 @@ def load_sploop_library():
     for name, argtypes in _SPLOOP_ARGTYPES.items():
         getattr(lib, name).argtypes = argtypes          # raises AttributeError if a declared symbol is missing
     _sploop = lib
+    return lib
+
+
+def load_sgloop_library():
+    """Load libimx_sgloop.so (built beside libimx.so by the same make); libimx.so is loaded first: it makes the handles."""
+    global _sgloop
+    if _sgloop is not None:
+        return _sgloop
+    load_library()
+    if not os.path.exists(SGLOOP_LIB_PATH):
+        raise RuntimeError(f"libimx_sgloop.so not found at {SGLOOP_LIB_PATH}: build it with `make -C image-matching_amd/csrc`")
+    lib = ctypes.CDLL(SGLOOP_LIB_PATH)
+    for name, argtypes in _SGLOOP_ARGTYPES.items():
+        getattr(lib, name).argtypes = argtypes          # raises AttributeError if a declared symbol is missing
+    _sgloop = lib
     return lib

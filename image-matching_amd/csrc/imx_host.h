@@ -1,7 +1,7 @@
 // imx_host.h -- internal header of the host units of libimx.so (imx_api.cpp, imx_options.cpp, imx_weights.cpp, imx_superpoint.cpp,
 // imx_superglue.cpp, imx_trainpairs.cpp), of libimx_train.so (imx_sptrain.cpp, imx_spgrad.cpp, imx_otgrad.cpp, imx_mhagrad.cpp,
 // imx_lingrad.cpp, imx_bngrad.cpp), of libimx_sgtrain.so (imx_scoregrad.cpp), of libimx_spnet.so (imx_conv3grad.cpp), of
-// libimx_spnorm.so (imx_bn2dgrad.cpp), of libimx_sppool.so (imx_poolgrad.cpp), of libimx_photo.so (imx_photo.cpp) and of libimx_sploop.so (imx_sploop.cpp), which work on the
+// libimx_spnorm.so (imx_bn2dgrad.cpp), of libimx_sppool.so (imx_poolgrad.cpp), of libimx_photo.so (imx_photo.cpp), of libimx_sploop.so (imx_sploop.cpp) and of libimx_sgloop.so (imx_sgloop.cpp), which work on the
 // handles libimx.so makes: the handle,
 // its weight sets and workspaces, the launch helpers, the weights-derived guards of the fp16-plane forms, and the stage functions
 // libimx.so's entry points call.  Nothing here is exported (hidden visibility; imx.map).

@@ -22,6 +22,9 @@ struct OtArgs {
   int* cnt_bin;                             // (B,N0+N1+1): listings on the dustbin row (y = 0..n, the corner at n), then on the dustbin column
   float* binv;                              // (B,N0+N1+1): C-bar on the dustbin row, then on the dustbin column, for grad_bin
 };
+// the normaliser of Z = C + u_T + v_T - norm for a pair with counts m, n: ONE expression, shared by otgrad.hip (the loss reads Z through it)
+// and sgloop.hip (the matches are extracted from the same Z), so that both form the same bits
+__device__ __forceinline__ float ot_norm(int m, int n) { return -logf((float)(m + n)); }
 constexpr int kOtFlagIndex = 1;             // bit 0 of flag: a listed index outside the coupling matrix (the entry contributes nothing)
 
 hipError_t launch_ot_init(const OtArgs& a, hipStream_t s);            // u_0 = v_0 = 0, the counts zeroed (and grad, which first holds counts)

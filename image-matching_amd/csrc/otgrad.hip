@@ -37,7 +37,7 @@ __device__ inline Pair pair_of(const OtArgs& a, int b) {
   p.n = clampi(a.n1 ? a.n1[b] : a.N1, 0, a.N1);
   p.ok = p.m > 0 && p.n > 0;
   p.alpha = *a.bin;
-  p.norm = -logf((float)(p.m + p.n));
+  p.norm = ot_norm(p.m, p.n);
   p.lmu_last = logf((float)p.n) + p.norm;
   p.lnu_last = logf((float)p.m) + p.norm;
   return p;

@@ -51,6 +51,7 @@ class Engine:
         self.sppool = L.load_sppool_library()      # MaxPool2d(2) and the descriptor normalisation of that step (include/imx_sppool.h), likewise
         self.photo = L.load_photo_library()        # the photometric augmentation of that step's data (include/imx_photo.h), likewise
         self.sploop = L.load_sploop_library()      # the soft labels and the optimiser step of the training loop (include/imx_sploop.h), likewise
+        self.sgloop = L.load_sgloop_library()      # the matches of SuperGlue's training forward from the loss's Sinkhorn (include/imx_sgloop.h), likewise
         if not torch.cuda.is_available():
             raise ImxError("image_matching_amd needs a ROCm GPU (torch.cuda.is_available() is False); "
                            "there is no CPU fallback on the product path")
@@ -757,35 +758,104 @@ class Engine:
         int32 as gt_matches writes them, n0 / n1 (B) int32 counts or None = all, gout (B) upstream cotangents or None = 1.  Returns
         dict: loss (B), flag (B) int32 (bit 0: a listed index outside the coupling matrix) and, unless want_grad is False, grad_scores
         (B,N0,N1) (0 past the counts) and grad_bin (B).  No host synchronisation."""
+        a = self._ot_args("ot_match_loss_grad", scores, bin_score, all_matches, n_all, n0, n1, gout, want_grad)
+        res = a["res"]
+        self._check(self.train.imx_ot_match_loss_grad(self.handle, a["B"], _ptr(a["scores"]), a["N0"], a["N1"], _ptr(a["n0"]), _ptr(a["n1"]),
+                                                    _ptr(a["bin_score"]), int(iters), _ptr(a["all_matches"]), _ptr(a["n_all"]), a["L"],
+                                                    _ptr(a["gout"]), _ptr(res["loss"]), _ptr(res.get("grad_scores")), _ptr(res.get("grad_bin")),
+                                                    _ptr(res["flag"]), _stream(self.device)))
+        return res
+
+    def _ot_args(self, who, scores, bin_score, all_matches, n_all, n0, n1, gout, want_grad):
+        """the checked, device-resident arguments of ot_match_loss_grad and of ot_match_loss_grad_matches, and the output dict"""
         dev = self.device
         if scores.dim() != 3:
-            raise ImxError(f"ot_match_loss_grad: scores must be (B,N0,N1), got {tuple(scores.shape)}")
+            raise ImxError(f"{who}: scores must be (B,N0,N1), got {tuple(scores.shape)}")
         B, N0, N1 = (int(v) for v in scores.shape)
-        scores = self._f32(scores, (B, N0, N1), "ot_match_loss_grad: scores")
+        scores = self._f32(scores, (B, N0, N1), f"{who}: scores")
         if not isinstance(bin_score, torch.Tensor):
             bin_score = torch.full((1,), float(bin_score), dtype=torch.float32, device=dev)
         if bin_score.numel() != 1:
-            raise ImxError(f"ot_match_loss_grad: bin_score must hold one element, got {tuple(bin_score.shape)}")
+            raise ImxError(f"{who}: bin_score must hold one element, got {tuple(bin_score.shape)}")
         bin_score = bin_score.detach().to(dev, torch.float32).reshape(1).contiguous()
         all_matches = all_matches.to(dev, torch.int64).contiguous()
         if all_matches.dim() != 3 or all_matches.shape[0] != B or all_matches.shape[1] != 2:
-            raise ImxError(f"ot_match_loss_grad: all_matches must be (B,2,L) with B = {B}, got {tuple(all_matches.shape)}")
+            raise ImxError(f"{who}: all_matches must be (B,2,L) with B = {B}, got {tuple(all_matches.shape)}")
         Lc = int(all_matches.shape[2])
-        n_all = self._counts(n_all, B, "ot_match_loss_grad: n_all")
-        n0, n1 = self._counts(n0, B, "ot_match_loss_grad: n0"), self._counts(n1, B, "ot_match_loss_grad: n1")
+        n_all = self._counts(n_all, B, f"{who}: n_all")
+        n0, n1 = self._counts(n0, B, f"{who}: n0"), self._counts(n1, B, f"{who}: n1")
         if n_all is None:
-            raise ImxError("ot_match_loss_grad: n_all is required")
+            raise ImxError(f"{who}: n_all is required")
         if gout is not None:
             gout = gout.to(dev, torch.float32).contiguous()
             if gout.numel() != B:
-                raise ImxError(f"ot_match_loss_grad: {gout.numel()} cotangents for a batch of {B}")
+                raise ImxError(f"{who}: {gout.numel()} cotangents for a batch of {B}")
         res = {"loss": torch.empty(B, dtype=torch.float32, device=dev), "flag": torch.empty(B, dtype=torch.int32, device=dev)}
         if want_grad:
             res["grad_scores"] = torch.empty(B, N0, N1, dtype=torch.float32, device=dev)
             res["grad_bin"] = torch.empty(B, dtype=torch.float32, device=dev)
-        self._check(self.train.imx_ot_match_loss_grad(self.handle, B, _ptr(scores), N0, N1, _ptr(n0), _ptr(n1), _ptr(bin_score), int(iters),
-                                                    _ptr(all_matches), _ptr(n_all), Lc, _ptr(gout), _ptr(res["loss"]),
-                                                    _ptr(res.get("grad_scores")), _ptr(res.get("grad_bin")), _ptr(res["flag"]), _stream(dev)))
+        return {"B": B, "N0": N0, "N1": N1, "L": Lc, "scores": scores, "bin_score": bin_score, "all_matches": all_matches, "n_all": n_all,
+                "n0": n0, "n1": n1, "gout": gout, "res": res}
+
+    # ------------------------------------------------------------------ the matches of the training forward (include/imx_sgloop.h)
+    def _match_outputs(self, who, B, N0, N1, gt0, res):
+        """matches0/1 (int64), matching_scores0/1 (fp32) and, with gt0 (B,N0) int64, stats (B,3) int32, added to res; returns gt0 on the device"""
+        dev = self.device
+        res.update({"matches0": torch.empty(B, N0, dtype=torch.int64, device=dev), "matches1": torch.empty(B, N1, dtype=torch.int64, device=dev),
+                    "matching_scores0": torch.empty(B, N0, dtype=torch.float32, device=dev),
+                    "matching_scores1": torch.empty(B, N1, dtype=torch.float32, device=dev)})
+        if gt0 is None:
+            return None
+        gt0 = gt0.to(dev, torch.int64).contiguous()
+        if tuple(gt0.shape) != (B, N0):
+            raise ImxError(f"{who}: gt0 must be (B,N0) = ({B},{N0}), got {tuple(gt0.shape)}")
+        res["stats"] = torch.empty(B, 3, dtype=torch.int32, device=dev)
+        return gt0
+
+    @staticmethod
+    def _threshold(who, threshold):
+        threshold = float(threshold)
+        if math.isnan(threshold):
+            raise ImxError(f"{who}: threshold is NaN")
+        return threshold
+
+    def assignment_matches(self, scores, u=None, v=None, threshold=0.2, n0=None, n1=None, gt0=None):
+        """The extraction of superglue/models/superglue_train.py:276-286 from scores (B,N0,N1) fp32 and the final potentials u (B,N0+1), v
+        (B,N1+1) of the log-domain Sinkhorn (None = zeros): Z = ((scores + u) + v) - norm element by element, never stored.  n0 / n1 (B)
+        int32 counts or None = all, gt0 (B,N0) int64 or None.  Returns dict: matches0 (B,N0), matches1 (B,N1) int64 (-1 = none, and past
+        the counts), matching_scores0/1 fp32 (0 past the counts) and, with gt0, stats (B,3) int32 = [gt0 >= 0, matches0 > -1, matches0 ==
+        gt0 >= 0] over the valid rows.  Among equal values the lowest index wins.  No host synchronisation."""
+        who = "assignment_matches"
+        if scores.dim() != 3:
+            raise ImxError(f"{who}: scores must be (B,N0,N1), got {tuple(scores.shape)}")
+        B, N0, N1 = (int(s) for s in scores.shape)
+        scores = self._f32(scores, (B, N0, N1), f"{who}: scores")
+        u = None if u is None else self._f32(u, (B, N0 + 1), f"{who}: u")
+        v = None if v is None else self._f32(v, (B, N1 + 1), f"{who}: v")
+        n0, n1 = self._counts(n0, B, f"{who}: n0"), self._counts(n1, B, f"{who}: n1")
+        threshold = self._threshold(who, threshold)
+        res = {}
+        gt0 = self._match_outputs(who, B, N0, N1, gt0, res)
+        self._check(self.sgloop.imx_assignment_matches(self.handle, B, _ptr(scores), N0, N1, _ptr(n0), _ptr(n1), _ptr(u), _ptr(v), threshold,
+                                                       _ptr(gt0), _ptr(res["matches0"]), _ptr(res["matches1"]), _ptr(res["matching_scores0"]),
+                                                       _ptr(res["matching_scores1"]), _ptr(res.get("stats")), _stream(self.device)))
+        return res
+
+    def ot_match_loss_grad_matches(self, scores, bin_score, all_matches, n_all, iters, n0=None, n1=None, gout=None, want_grad=True, threshold=0.2,
+                                   gt0=None):
+        """ot_match_loss_grad and assignment_matches on the potentials of that very Sinkhorn, one call: the arguments of ot_match_loss_grad
+        plus threshold and gt0.  Returns its dict -- loss, flag, grad_scores and grad_bin with the same bits -- plus matches0/1,
+        matching_scores0/1 and, with gt0, stats.  No host synchronisation."""
+        who = "ot_match_loss_grad_matches"
+        a = self._ot_args(who, scores, bin_score, all_matches, n_all, n0, n1, gout, want_grad)
+        res = a["res"]
+        threshold = self._threshold(who, threshold)
+        gt0 = self._match_outputs(who, a["B"], a["N0"], a["N1"], gt0, res)
+        self._check(self.sgloop.imx_ot_match_loss_grad_matches(
+            self.handle, a["B"], _ptr(a["scores"]), a["N0"], a["N1"], _ptr(a["n0"]), _ptr(a["n1"]), _ptr(a["bin_score"]), int(iters),
+            _ptr(a["all_matches"]), _ptr(a["n_all"]), a["L"], _ptr(a["gout"]), _ptr(res["loss"]), _ptr(res.get("grad_scores")),
+            _ptr(res.get("grad_bin")), _ptr(res["flag"]), threshold, _ptr(gt0), _ptr(res["matches0"]), _ptr(res["matches1"]),
+            _ptr(res["matching_scores0"]), _ptr(res["matching_scores1"]), _ptr(res.get("stats")), _stream(self.device)))
         return res
 
     # ------------------------------------------------------------------ the GNN's attention, training form (include/imx_train.h)

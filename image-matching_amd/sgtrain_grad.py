@@ -8,6 +8,9 @@ the network.
     loss = match_loss(engine, scores, self.bin_score, all_matches, n_all, iters).mean()
     loss.backward()
 
+`match_loss_matches(...)` returns the same loss together with the matches and matching scores the reference's forward reports
+(superglue_train.py:276-286), extracted from that same Sinkhorn's final potentials (include/imx_sgloop.h).
+
 The attention of the GNN (superglue_train.py:82-86) is here as well, forward and backward from libimx (include/imx_train.h): inside the
 reference's MultiHeadedAttention.forward,
 
@@ -77,6 +80,46 @@ def match_loss(engine, scores, bin_score, all_matches, n_all, iters, n0=None, n1
     """The per-pair loss (B) of superglue_train.py:289-299 on scores (B,N0,N1) = einsum(mdesc0, mdesc1) / sqrt(d), replacing lines
     271-299 of the reference's forward; `.backward()` reaches scores and bin_score."""
     return ot_match_loss.apply(engine, scores, bin_score, all_matches, n_all, int(iters), n0, n1)[0]
+
+
+class ot_match_loss_matches(torch.autograd.Function):
+    """ot_match_loss_matches.apply(engine, scores, bin_score, all_matches, n_all, iters, threshold, n0, n1, gt0): ot_match_loss with the
+    matches of superglue_train.py:276-286 taken from the SAME Sinkhorn (Engine.ot_match_loss_grad_matches, include/imx_sgloop.h).
+    Returns (loss (B), flag, matches0, matches1, matching_scores0, matching_scores1, stats): the loss is differentiable with respect to
+    scores and bin_score, with the bits and the gradients of ot_match_loss; everything else is marked non-differentiable.  stats (B,3)
+    int32 needs gt0 (B,N0) int64; without it an empty (B,0) tensor stands in its place."""
+
+    @staticmethod
+    def forward(ctx, engine, scores, bin_score, all_matches, n_all, iters, threshold, n0=None, n1=None, gt0=None):
+        _require(scores, "ot_match_loss_matches: scores")
+        _require(bin_score, "ot_match_loss_matches: bin_score")
+        res = engine.ot_match_loss_grad_matches(scores, bin_score, all_matches, n_all, iters, n0=n0, n1=n1, threshold=threshold, gt0=gt0)
+        ctx.save_for_backward(res["grad_scores"], res["grad_bin"])
+        ctx.bin_shape = bin_score.shape
+        stats = res["stats"] if "stats" in res else torch.empty(scores.shape[0], 0, dtype=torch.int32, device=scores.device)
+        extra = (res["flag"], res["matches0"], res["matches1"], res["matching_scores0"], res["matching_scores1"], stats)
+        ctx.mark_non_differentiable(*extra)
+        return (res["loss"],) + extra
+
+    @staticmethod
+    @once_differentiable                                                 # the saved gradients are constants: no second derivative here
+    def backward(ctx, grad_loss, *_unused):
+        gs, gb = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        return (None, gs * grad_loss.reshape(-1, 1, 1) if need[1] else None,
+                (gb * grad_loss.reshape(-1)).sum().reshape(ctx.bin_shape) if need[2] else None) + (None,) * 7
+
+
+def match_loss_matches(engine, scores, bin_score, all_matches, n_all, iters, threshold, n0=None, n1=None, gt0=None):
+    """match_loss and the reference's matches in one call, one Sinkhorn: (loss (B), {matches0, matches1, matching_scores0,
+    matching_scores1[, stats]}).  `.backward()` of the loss reaches scores and bin_score exactly as match_loss's does; the dict's tensors
+    require no grad."""
+    loss, _flag, m0, m1, ms0, ms1, stats = ot_match_loss_matches.apply(engine, scores, bin_score, all_matches, n_all, int(iters), float(threshold),
+                                                                     n0, n1, gt0)
+    out = {"matches0": m0, "matches1": m1, "matching_scores0": ms0, "matching_scores1": ms1}
+    if gt0 is not None:
+        out["stats"] = stats
+    return loss, out
 
 
 class mha(torch.autograd.Function):

@@ -159,7 +159,9 @@ class SuperGlueTrainable(nn.Module):
             raise ImxError("SuperGlueTrainable was built without an engine: there is no CPU path")
         return self.engine
 
-    def _loss_and_scores(self, kpts0, scores0, desc0, kpts1, scores1, desc1, all_matches, n_all, shape0, shape1, n0, n1):
+    def _loss_and_scores(self, kpts0, scores0, desc0, kpts1, scores1, desc1, all_matches, n_all, shape0, shape1, n0, n1, matches=False, gt0=None):
+        """(loss (B), scores); with matches=True (loss, scores, the dict of match_loss_matches) from the fused call -- the network part is
+        the same code, so the loss and every gradient have the same bits either way"""
         eng = self._engine()
         dev = eng.device
         cnt = lambda c: None if c is None else torch.as_tensor(c).to(dev, torch.int32).contiguous()
@@ -176,6 +178,10 @@ class SuperGlueTrainable(nn.Module):
         mdesc0 = G.conv1d(eng, desc0, self.final_proj.weight, self.final_proj.bias, n=n0)
         mdesc1 = G.conv1d(eng, desc1, self.final_proj.weight, self.final_proj.bias, n=n1)
         scores = G.scores(eng, mdesc0, mdesc1, n0, n1)
+        if matches:
+            loss, found = G.match_loss_matches(eng, scores, self.bin_score, all_matches, cnt(n_all), self.config['sinkhorn_iterations'],
+                                               self.config['match_threshold'], n0, n1, gt0)
+            return loss, scores, found
         return G.match_loss(eng, scores, self.bin_score, all_matches, cnt(n_all), self.config['sinkhorn_iterations'], n0, n1), scores
 
     def forward_pairs(self, kpts0, scores0, desc0, kpts1, scores1, desc1, all_matches, n_all, shape0, shape1, n0=None, n1=None):
@@ -185,6 +191,15 @@ class SuperGlueTrainable(nn.Module):
         by a kernel and may hold anything.  BatchNorm follows the module's mode and updates its buffers in place in train mode."""
         return self._loss_and_scores(kpts0, scores0, desc0, kpts1, scores1, desc1, all_matches, n_all, shape0, shape1, n0, n1)[0]
 
+    def forward_pairs_matches(self, kpts0, scores0, desc0, kpts1, scores1, desc1, all_matches, n_all, shape0, shape1, n0=None, n1=None, gt0=None):
+        """forward_pairs with what the reference's forward reports beside the loss: (loss (B), {matches0 (B,N0), matches1 (B,N1) int64,
+        matching_scores0, matching_scores1 fp32[, stats (B,3) int32 with gt0 (B,N0) int64]}), the matches extracted from the loss's own
+        Sinkhorn (include/imx_sgloop.h).  The loss and its gradients have forward_pairs' bits; the dict's tensors require no grad.  Past
+        the counts matches are -1 and scores 0."""
+        loss, _, found = self._loss_and_scores(kpts0, scores0, desc0, kpts1, scores1, desc1, all_matches, n_all, shape0, shape1, n0, n1,
+                                               matches=True, gt0=gt0)
+        return loss, found
+
     def forward(self, data, want_matches=True):
         """The reference's forward on one sample of GlueSparse as the training loop hands it over: descriptors{0,1} (d,1,N), keypoints{0,1}
         (1,1,N,2), scores{0,1} (N,1), all_matches (2,1,L), image{0,1} (only .shape).  Returns 'loss' (shape (1,)) and 'skip_train': False;
@@ -192,7 +207,8 @@ class SuperGlueTrainable(nn.Module):
 
         want_matches adds 'matches0/1' and 'matching_scores0/1', formed under torch.no_grad() by a PyTorch restatement of the optimal
         transport and the mutual-argmax extraction on the detached scores: that is a SECOND Sinkhorn, in PyTorch, beside the library's
-        own inside the loss.  The reference's loop reads them for its periodic visualisation only: a training loop passes False."""
+        own inside the loss.  want_matches="loss" returns the same keys from the fused call instead (forward_pairs_matches): ONE Sinkhorn,
+        the loss's, and the loss and every gradient keep the bits of want_matches=False.  A training loop passes "loss" or False."""
         desc0, desc1 = data['descriptors0'].transpose(0, 1).contiguous(), data['descriptors1'].transpose(0, 1).contiguous()
         kpts0, kpts1 = (torch.reshape(data[k], (1, data[k].numel() // 2, 2)) for k in ('keypoints0', 'keypoints1'))     # (an empty side too)
         if kpts0.shape[1] == 0 or kpts1.shape[1] == 0:                   # no keypoints (:238-246)
@@ -207,6 +223,12 @@ class SuperGlueTrainable(nn.Module):
         dev = self._engine().device
         all_matches = data['all_matches'].permute(1, 0, 2).to(dev, torch.int64).contiguous()      # (1, 2, L)
         n_all = torch.full((1,), all_matches.shape[2], dtype=torch.int32, device=dev)
+        if isinstance(want_matches, str):
+            if want_matches != "loss":
+                raise ImxError(f"SuperGlueTrainable.forward: want_matches must be True, False or 'loss', got {want_matches!r}")
+            loss, _, found = self._loss_and_scores(kpts0, torch.transpose(data['scores0'], 0, 1), desc0, kpts1, torch.transpose(data['scores1'], 0, 1),
+                                                   desc1, all_matches, n_all, data['image0'].shape, data['image1'].shape, None, None, matches=True)
+            return {'loss': loss, 'skip_train': False, **{k: v[0] for k, v in found.items()}}
         loss, scores = self._loss_and_scores(kpts0, torch.transpose(data['scores0'], 0, 1), desc0, kpts1, torch.transpose(data['scores1'], 0, 1),
                                              desc1, all_matches, n_all, data['image0'].shape, data['image1'].shape, None, None)
         out = {'loss': loss, 'skip_train': False}

@@ -1,0 +1,132 @@
+#!/usr/bin/env python
+"""The reference's superpoint_glue_train.py on the GPU: SuperGlue trained on warped pairs of one image directory, SuperPoint's keypoints
+and descriptors and the ground-truth assignment from datasets/GlueSparse.py, the step through sgtrain_model.SuperGlueTrainable (every
+layer in the libraries), the loop, the checkpoints, the log and the match pictures through superglue/train_loop.py.
+
+    python superpoint_glue_train.py --synthetic 4 --epoch 1
+
+The flags are the reference's, with its names and defaults and with the types repaired: --keypoint_encoder and --resize are lists of
+ints, --learning_rate a float, --resume, --shuffle and --show_keypoints booleans (`--resume`, `--resume true`, `--shuffle false`).  The
+checkpoint to resume from is <Result_dir>/<checkpoints_dir>/<checkpoints_name> (the reference's line names an undefined variable).
+Not in the reference: --synthetic N (N synthetic images and synthetic SuperPoint weights, no dataset), --iters K (stop after K steps,
+with a checkpoint), --seed (of the shuffle and of the warps) and --optimizer flat|torch.
+
+Scalars go to tensorboardX's SummaryWriter where that package is installed, otherwise to <Result_dir>/logdir/scalars.jsonl.  One GPU."""
+import argparse
+import json
+import os
+
+
+def _boolean(v):
+    if isinstance(v, bool):
+        return v
+    if v.lower() in ("1", "true", "yes", "y", "on"):
+        return True
+    if v.lower() in ("0", "false", "no", "n", "off"):
+        return False
+    raise argparse.ArgumentTypeError(f"expected a boolean, got {v!r}")
+
+
+def build_parser():
+    parser = argparse.ArgumentParser(description='Image pair matching and pose evaluation with SuperGlue', formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    parser.add_argument('--image_path', type=str, default='datasets/ALLSS/', help='Path to the directory of training imgs.')
+    parser.add_argument('--Result_dir', type=str, default='Results/ALLSS/superglue_descriptor_128', help='Path to the directory')
+    # base parameter
+    parser.add_argument('--epoch', type=int, default=200, help='Number of epoches')
+    parser.add_argument('--batch_size', type=int, default=1, help='batch_size')
+    parser.add_argument('--learning_rate', type=float, default=0.0001, help='Learning rate')
+    parser.add_argument('--shuffle', type=_boolean, nargs='?', const=True, default=True, help='Shuffle ordering of pairs before processing')
+    parser.add_argument('--show_keypoints', type=_boolean, nargs='?', const=True, default=True, help='Plot the keypoints in addition to the matches')
+    parser.add_argument('--viz_extension', type=str, default='png', choices=['png', 'pdf'], help='visualization file extension.Use pdf for highest-quality')
+    # model hyper parameter
+    parser.add_argument('--superpoint_weights', type=str, default="superpoint/models/weights/superPointNet_allss_descriptor_128.pth.tar")
+    parser.add_argument('--descriptor_dim', type=int, default=128, help='The dimension of feature descriptor')
+    parser.add_argument('--keypoint_encoder', type=int, nargs='+', default=[32, 64, 128], help='The dimension of keypoint encoder')
+    parser.add_argument('--max_keypoints', type=int, default=1200, help='Maximum number of keypoints detected by Superpoint (\'-1\' keeps all keypoints)')
+    parser.add_argument('--keypoint_threshold', type=float, default=0.005, help='SuperPoint keypoint detector confidence threshold')
+    parser.add_argument('--nms_radius', type=int, default=4, help='SuperPoint Non Maximum Suppression (NMS) radius (Must be positive)')
+    parser.add_argument('--sinkhorn_iterations', type=int, default=30, help='Number of Sinkhorn iterations performed by SuperGlue')
+    parser.add_argument('--match_threshold', type=float, default=0.2, help='SuperGlue match threshold')
+    parser.add_argument('--resize', type=int, nargs=2, default=[640, 480], help='The size of image')
+    # pretrain or checkpoint model
+    parser.add_argument('--pretrain_weights', type=str, default='', help='SuperGlue official weights')
+    parser.add_argument('--checkpoints_dir', type=str, default='checkpoints/', help='models saved here')
+    parser.add_argument('--checkpoints_name', type=str, default='', help='checkpoint model name')
+    parser.add_argument('--save_epoch_freq', type=int, default=5, help='frequency of saving checkpoints')
+    parser.add_argument('--resume', type=_boolean, nargs='?', const=True, default=False, help='if specified, the model start from checkpoints')
+    # not in the reference
+    parser.add_argument('--synthetic', type=int, default=0, help='train on this many synthetic images (no dataset, synthetic SuperPoint weights)')
+    parser.add_argument('--iters', type=int, default=0, help='stop after this many optimiser steps, with a checkpoint (0 = run every epoch)')
+    parser.add_argument('--seed', type=int, default=0, help='seed of the shuffle and of the warp sampler')
+    parser.add_argument('--optimizer', type=str, default='flat', choices=['flat', 'torch'], help='one-launch Adam on a flat arena, or torch.optim.Adam')
+    return parser
+
+
+def configs(opt):
+    """the reference's two config dicts (:56-70)"""
+    return {
+        'superpoint': {'weights': opt.superpoint_weights, 'descriptor_dim': opt.descriptor_dim, 'nms_radius': opt.nms_radius,
+                       'keypoint_threshold': opt.keypoint_threshold, 'max_keypoints': opt.max_keypoints},
+        'superglue': {'descriptor_dim': opt.descriptor_dim, 'keypoint_encoder': opt.keypoint_encoder,
+                      'sinkhorn_iterations': opt.sinkhorn_iterations, 'match_threshold': opt.match_threshold},
+    }
+
+
+def checkpoint_path(opt):
+    return os.path.join(opt.Result_dir, opt.checkpoints_dir, opt.checkpoints_name)
+
+
+def main(argv=None):
+    opt = build_parser().parse_args(argv)
+    print(opt)
+    import torch
+
+    from image_matching_amd.datasets.GlueSparse import GlueSparse
+    from image_matching_amd.scalars import make_writer
+    from image_matching_amd.superglue.train_loop import SuperGlueTrainer
+
+    device = torch.device('cuda:0')
+    synthetic = opt.synthetic > 0
+    if synthetic and opt.max_keypoints == 1200:
+        opt.max_keypoints, opt.resize = 256, [320, 240]
+    if opt.max_keypoints <= 0:
+        raise SystemExit("--max_keypoints must be positive: the batched data path writes fixed-size tensors")
+    config = configs(opt)
+    if synthetic:
+        from superglue_export_pairs import SyntheticPairs
+        train_set = SyntheticPairs(opt.synthetic, {**config['superpoint'], 'weights': None}, opt.resize, device)
+    else:
+        train_set = GlueSparse(os.path.join(opt.image_path, 'train'), config['superpoint'], opt.resize, device)
+    train_set.seed = opt.seed
+
+    writer = make_writer(opt.Result_dir + '/logdir')
+    trainer = SuperGlueTrainer(config['superglue'], train_set, train_set._engine(), optimizer=opt.optimizer, lr=opt.learning_rate,
+                               batch_size=opt.batch_size, shuffle=opt.shuffle, seed=opt.seed, result_dir=opt.Result_dir, writer=writer,
+                               show_keypoints=opt.show_keypoints, viz_extension=opt.viz_extension, max_steps=opt.iters)
+
+    if opt.pretrain_weights in ['indoor', 'outdoor']:
+        import image_matching_amd
+        path_pretrain = os.path.join(os.path.dirname(image_matching_amd.__file__), 'superglue', 'models', 'weights', 'superglue_{}.pth'.format(opt.pretrain_weights))
+        if not os.path.exists(path_pretrain):
+            raise SystemExit(f"--pretrain_weights {opt.pretrain_weights}: {path_pretrain} is not there (the official files are not shipped)")
+        trainer.net.load_state_dict(torch.load(path_pretrain, map_location=device))
+        print('Loaded SuperGlue official model (\"{}\" weights)'.format(opt.pretrain_weights))
+
+    if opt.resume:
+        trainer.resume(checkpoint_path(opt))
+        print('Loaded checkpoint model (\"{}\" weights)'.format(opt.checkpoints_name))
+
+    eval_output_dir = os.path.join(opt.Result_dir, 'match')
+    os.makedirs(eval_output_dir, exist_ok=True)
+    print('Will write visualization images to', 'directory \"{}\"'.format(eval_output_dir))
+
+    trainer.train(opt.epoch)
+    torch.cuda.synchronize()
+    writer.close()
+    ckpt_dir = os.path.join(opt.Result_dir, 'checkpoints')
+    print(json.dumps({"epoch": trainer.epoch, "steps": trainer.steps, "checkpoints": sorted(os.listdir(ckpt_dir)) if os.path.isdir(ckpt_dir) else [],
+                      "last": trainer.history[-1] if trainer.history else None}))
+
+
+if __name__ == '__main__':
+    main()

@@ -16,28 +16,7 @@ import os
 import numpy as np
 import torch
 
-
-class JsonlWriter:
-    """add_scalar(tag, value, step) -> one JSON line: what stands in for tensorboardX.SummaryWriter where it is not installed"""
-
-    def __init__(self, path):
-        self.f = open(path, "a")
-
-    def add_scalar(self, tag, value, step):
-        self.f.write(json.dumps({"tag": tag, "value": float(value), "step": int(step)}) + "\n")
-        self.f.flush()
-
-    def close(self):
-        self.f.close()
-
-
-def make_writer(output_dir):
-    try:
-        from tensorboardX import SummaryWriter
-        return SummaryWriter(output_dir)
-    except ImportError:
-        logging.info("tensorboardX is not installed: scalars go to %s", os.path.join(output_dir, "scalars.jsonl"))
-        return JsonlWriter(os.path.join(output_dir, "scalars.jsonl"))
+from image_matching_amd.scalars import JsonlWriter, make_writer  # noqa: F401  (shared with superpoint_glue_train.py)
 
 
 if __name__ == '__main__':
