@@ -1,6 +1,7 @@
 """ctypes binding of libimx.so (C ABI: include/imx.h), libimx_train.so (include/imx_train.h), libimx_sgtrain.so
 (include/imx_sgtrain.h), libimx_spnet.so (include/imx_spnet.h), libimx_spnorm.so (include/imx_spnorm.h), libimx_sppool.so (include/imx_sppool.h),
-libimx_photo.so (include/imx_photo.h), libimx_sploop.so (include/imx_sploop.h) and libimx_sgloop.so (include/imx_sgloop.h).  There is no CPU fallback: if the library is missing or no GPU is present the product path raises."""
+libimx_photo.so (include/imx_photo.h), libimx_sploop.so (include/imx_sploop.h), libimx_sgloop.so (include/imx_sgloop.h) and libimx_homog.so
+(include/imx_homog.h).  There is no CPU fallback: if the library is missing or no GPU is present the product path raises."""
 import ctypes
 import os
 
@@ -132,6 +133,16 @@ _SGLOOP_ARGTYPES = {
 }
 SGLOOP_EXPORTS = tuple(_SGLOOP_ARGTYPES)
 
+# libimx_homog.so (C ABI: include/imx_homog.h): the batched RANSAC homography fit on matched keypoints and the corner error of a fit against a
+# known warp, on libimx.so's handles -- a library of its own because the other nine symbol tables are pinned to their headers; name -> argtypes
+HOMOG_LIB_PATH = os.path.join(_HERE, "libimx_homog.so")
+_u32 = ctypes.c_uint32
+_HOMOG_ARGTYPES = {
+    "imx_estimate_homography": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f64, _i32, _i32, _u32, _vp, _vp, _vp, _vp, _vp],
+    "imx_homography_corner_error": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp],
+}
+HOMOG_EXPORTS = tuple(_HOMOG_ARGTYPES)
+
 _lib = None
 _train = None
 _sgtrain = None
@@ -141,6 +152,7 @@ _sppool = None
 _photo = None
 _sploop = None
 _sgloop = None
+_homog = None
 
 
 def load_library():
@@ -322,4 +334,19 @@ def load_sgloop_library():
     for name, argtypes in _SGLOOP_ARGTYPES.items():
         getattr(lib, name).argtypes = argtypes          # raises AttributeError if a declared symbol is missing
     _sgloop = lib
+    return lib
+
+
+def load_homog_library():
+    """Load libimx_homog.so (built beside libimx.so by the same make); libimx.so is loaded first: it makes the handles."""
+    global _homog
+    if _homog is not None:
+        return _homog
+    load_library()
+    if not os.path.exists(HOMOG_LIB_PATH):
+        raise RuntimeError(f"libimx_homog.so not found at {HOMOG_LIB_PATH}: build it with `make -C image-matching_amd/csrc`")
+    lib = ctypes.CDLL(HOMOG_LIB_PATH)
+    for name, argtypes in _HOMOG_ARGTYPES.items():
+        getattr(lib, name).argtypes = argtypes          # raises AttributeError if a declared symbol is missing
+    _homog = lib
     return lib

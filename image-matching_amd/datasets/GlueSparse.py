@@ -25,6 +25,15 @@ class GlueSparse(Dataset):
         self.superpoint = SuperPoint(sp_config).to(device)
         self.superpoint.eval()
 
+    @classmethod
+    def beside(cls, other, path):
+        """(not in the reference) a dataset over another directory that shares `other`'s SuperPoint, size and device: a validation set
+        beside a training set runs on the same engine and weights instead of loading a second copy"""
+        self = cls.__new__(cls)
+        self.__dict__.update(other.__dict__)          # everything the constructor set, whatever it sets: only the file list differs
+        self.files = [path + '/' + f for f in os.listdir(path)]
+        return self
+
     def __len__(self):
         return len(self.files)
 

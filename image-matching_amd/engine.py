@@ -52,6 +52,7 @@ class Engine:
         self.photo = L.load_photo_library()        # the photometric augmentation of that step's data (include/imx_photo.h), likewise
         self.sploop = L.load_sploop_library()      # the soft labels and the optimiser step of the training loop (include/imx_sploop.h), likewise
         self.sgloop = L.load_sgloop_library()      # the matches of SuperGlue's training forward from the loss's Sinkhorn (include/imx_sgloop.h), likewise
+        self.homog = L.load_homog_library()        # the RANSAC homography fit and the corner error (include/imx_homog.h), likewise
         if not torch.cuda.is_available():
             raise ImxError("image_matching_amd needs a ROCm GPU (torch.cuda.is_available() is False); "
                            "there is no CPU fallback on the product path")
@@ -271,6 +272,61 @@ class Engine:
                                                          B, K, float(ransac_thresh), int(hypotheses), int(seed) & 0xFFFFFFFF,
                                                          _ptr(M), _ptr(inl), _ptr(ninl), _stream(dev)))
         return M, inl[:, :K0], ninl
+
+    def estimate_homography(self, kpts0, kpts1, matches0, counts0=None, ransac_thresh=3.0, hypotheses=512, refine_iters=3, seed=0):
+        """Batched RANSAC homography fit on the GPU, the cv2.findHomography(mkpts0, mkpts1, cv2.RANSAC, thr) counterpart of
+        estimate_affine_partial (include/imx_homog.h): kpts0 (B,K0,2), kpts1 (B,K1,2) fp32, matches0 (B,K0) int64, counts0 (B) int32 or
+        None = K0.  Returns H (B,3,3) float64 mapping kpts0 to kpts1 with H[2,2] = 1 (all zeros = no fit), the winning hypothesis' inlier
+        mask (B,K0) uint8, n_inliers (B) int32 and best_h (B) int32 (-1 = no fit).  A pair's result does not depend on the batch around it.
+        No host synchronisation."""
+        who, dev = "estimate_homography", self.device
+        for name, t in (("kpts0", kpts0), ("kpts1", kpts1), ("matches0", matches0)):
+            if not isinstance(t, torch.Tensor) or t.device != dev:
+                raise ImxError(f"{who}: {name} must be a tensor on {dev}, got {getattr(t, 'device', type(t))}")
+        if matches0.dim() != 2 or matches0.dtype != torch.int64:
+            raise ImxError(f"{who}: matches0 must be (B,K0) int64, got {tuple(matches0.shape)} {matches0.dtype}")
+        B, K0 = (int(v) for v in matches0.shape)
+        if kpts0.dtype != torch.float32 or kpts1.dtype != torch.float32:
+            raise ImxError(f"{who}: keypoints must be float32, got {kpts0.dtype} and {kpts1.dtype}")
+        if tuple(kpts0.shape) != (B, K0, 2) or kpts1.dim() != 3 or kpts1.shape[0] != B or kpts1.shape[2] != 2:
+            raise ImxError(f"{who}: expected kpts0 ({B},{K0},2) and kpts1 ({B},K1,2), got {tuple(kpts0.shape)} and {tuple(kpts1.shape)}")
+        K1 = int(kpts1.shape[1])
+        if B < 1 or K0 < 1 or K1 < 1:
+            raise ImxError(f"{who}: empty input B={B} K0={K0} K1={K1}")
+        if counts0 is not None and not (isinstance(counts0, torch.Tensor) and counts0.dtype == torch.int32 and counts0.dim() == 1
+                                        and counts0.numel() == B and counts0.device == dev and counts0.is_contiguous()):
+            raise ImxError(f"{who}: counts0 must be a contiguous int32 tensor of {B} elements on {dev}")
+        thr = float(ransac_thresh)
+        if not (thr > 0.0 and math.isfinite(thr)):
+            raise ImxError(f"{who}: ransac_thresh must be positive and finite, got {ransac_thresh!r}")
+        kpts0, kpts1, matches0 = kpts0.contiguous(), kpts1.contiguous(), matches0.contiguous()
+        H = torch.empty(B, 3, 3, dtype=torch.float64, device=dev)
+        inl = torch.empty(B, K0, dtype=torch.uint8, device=dev)
+        ninl = torch.empty(B, dtype=torch.int32, device=dev)
+        best = torch.empty(B, dtype=torch.int32, device=dev)
+        self._check(self.homog.imx_estimate_homography(self.handle, _ptr(kpts0), _ptr(kpts1), _ptr(matches0), _ptr(counts0), B, K0, K1, thr,
+                                                       int(hypotheses), int(refine_iters), int(seed) & 0xFFFFFFFF, _ptr(H), _ptr(inl), _ptr(ninl),
+                                                       _ptr(best), _stream(dev)))
+        return H, inl, ninl, best
+
+    def homography_corner_error(self, H, H_gt, size_hw):
+        """The mean distance, in pixels, of the four corners of a (height, width) = size_hw image under H (B,3,3) and under H_gt (B,3,3;
+        a device tensor or host matrices), in float64 on the device: (B) float64, +inf where H is all zeros (a failed fit).  No host
+        synchronisation when H_gt is a tensor."""
+        who, dev = "homography_corner_error", self.device
+        if not isinstance(H, torch.Tensor) or H.device != dev or H.dtype != torch.float64 or H.dim() != 3 or tuple(H.shape[1:]) != (3, 3):
+            raise ImxError(f"{who}: H must be a (B,3,3) float64 tensor on {dev}, got {getattr(H, 'dtype', type(H))} "
+                           f"{tuple(getattr(H, 'shape', ()))} {getattr(H, 'device', None)}")
+        B = int(H.shape[0])
+        if B < 1:
+            raise ImxError(f"{who}: empty batch")
+        H, gt = H.contiguous(), self._matrices(H_gt, B, who)
+        height, width = (int(v) for v in size_hw)
+        if height < 1 or width < 1:
+            raise ImxError(f"{who}: bad image size {size_hw!r}")
+        err = torch.empty(B, dtype=torch.float64, device=dev)
+        self._check(self.homog.imx_homography_corner_error(self.handle, _ptr(H), _ptr(gt), B, width, height, _ptr(err), _stream(dev)))
+        return err
 
     def knn_ratio_match(self, desc0, desc1, ratio=0.7, n0=None, n1=None):
         """Exact 2-NN + ratio test (superpoint_flann_test.py:66-74 without FLANN's approximation).

@@ -13,7 +13,14 @@ keypoints, formed on the device.  The reference runs batch size 1 and `continue`
 loss 0 and zero gradients (imx_ot_match_loss_grad), and a batch of nothing but such pairs still takes an optimiser step with zero
 gradients: skipping it would need a host read inside the step.
 
-ONE GPU.  No validation epochs: the reference's loop has none."""
+Validation (not in the reference, whose loop has none): with a `val_dataset`, validate() runs after the checkpoint of every
+`val_interval`-th epoch.  It walks the validation set in index order under a fixed dataset seed -- every validation sees the same warps --
+in .eval() mode and under torch.no_grad(): forward_pairs_matches for the loss and the counts behind precision and recall, then the
+measure of the SuperPoint and SuperGlue papers for pairs related by a homography: Engine.estimate_homography on the predicted matches
+(include/imx_homog.h) and Engine.homography_corner_error against the known warp.  Everything accumulates on the device; ONE read-back
+per validation.  It changes no parameter, BatchNorm buffer, optimiser state, shuffle generator or seed of the training set.
+
+ONE GPU."""
 import os
 from collections.abc import Mapping
 from pathlib import Path
@@ -58,15 +65,23 @@ def _jet(values):
 
 
 class SuperGlueTrainer:
-    """SuperGlueTrainer(config, dataset, engine, optimizer="flat" | "torch", lr=1e-4, ...).  `config` is the SuperGlue config of the
+    """SuperGlueTrainer(config, dataset, engine, optimizer="flat" | "torch", lr=1e-4, ..., val_dataset=None, val_interval=1,
+    val_batch_size=None (= batch_size), val_thresh=3.0 (pixels, the RANSAC threshold of the validation's fit)).  `config` is the SuperGlue config of the
     reference's script (descriptor_dim, keypoint_encoder, sinkhorn_iterations, match_threshold[, GNN_layers]); `dataset` has
     batch(indices) and __len__ (datasets.GlueSparse); engine = None builds the parameters and the optimiser state only (save, resume and
     the state dicts work; a step raises)."""
 
     def __init__(self, config, dataset, engine, optimizer="flat", lr=1e-4, batch_size=1, shuffle=True, seed=0, result_dir=None, writer=None,
-                 log_interval=5, show_keypoints=True, viz_extension="png", max_steps=0, keep_losses=False):
+                 log_interval=5, show_keypoints=True, viz_extension="png", max_steps=0, keep_losses=False, val_dataset=None, val_interval=1,
+                 val_batch_size=None, val_thresh=3.0):
         if optimizer not in ("flat", "torch"):
             raise ValueError(f"SuperGlueTrainer: optimizer must be 'flat' or 'torch', got {optimizer!r}")
+        if int(val_interval) < 1:
+            raise ValueError(f"SuperGlueTrainer: val_interval must be at least 1 epoch, got {val_interval!r}")
+        if val_batch_size is not None and int(val_batch_size) < 1:
+            raise ValueError(f"SuperGlueTrainer: val_batch_size must be positive, got {val_batch_size!r}")
+        if not float(val_thresh) > 0.0 or float(val_thresh) == float("inf"):
+            raise ValueError(f"SuperGlueTrainer: val_thresh must be a positive number of pixels, got {val_thresh!r}")
         self.config, self.dataset, self.engine = dict(config or {}), dataset, engine
         self.net = SuperGlueTrainable(self.config, engine).train()
         self.optimizer_kind, self.lr = optimizer, float(lr)
@@ -86,6 +101,10 @@ class SuperGlueTrainer:
         self.history = []                   # (tag, step, value) of every scalar read back
         self.last = None                    # the last step's batch and matches, for the picture
         self._data_seed = None
+        self.val_dataset, self.val_interval, self.val_thresh = val_dataset, int(val_interval), float(val_thresh)
+        self.val_batch_size = self.batch_size if val_batch_size is None else int(val_batch_size)
+        self._val_seed = int(getattr(val_dataset, "seed", 0)) if val_dataset is not None else None      # the warps of EVERY validation
+        self.last_validation = None         # the scalars of the last validate(), a dict
         self._reset_accumulators()
 
     # ---------------------------------------------------------------------------------------------- one step
@@ -176,12 +195,76 @@ class SuperGlueTrainer:
                                         small_text=["Matches: {}".format(int(valid.sum())), stem])
         return str(path)
 
+    # ---------------------------------------------------------------------------------------------- validation
+    def _val_batches(self):
+        """the index lists of one validation pass: index order, every sample (no drop_last)"""
+        n = len(self.val_dataset)
+        return [list(range(i, min(i + self.val_batch_size, n))) for i in range(0, n, self.val_batch_size)]
+
+    def _validate_batch(self, b):
+        """one validation batch, under the caller's mode and grad setting: (per-pair loss (B), the dict of forward_pairs_matches, the
+        corner error (B) float64 of the homography fitted to matches0 against b['M']); nothing is read back"""
+        shape = tuple(b["image0"].shape[-2:])
+        per_pair, found = self.net.forward_pairs_matches(
+            b["keypoints0"], b["scores0"], b["descriptors0"].transpose(1, 2), b["keypoints1"], b["scores1"], b["descriptors1"].transpose(1, 2),
+            b["all_matches"], b["n_all"], shape, shape, n0=b["counts0"], n1=b["counts1"], gt0=b["gt0"])
+        H, _, _, _ = self.engine.estimate_homography(b["keypoints0"].float().contiguous(), b["keypoints1"].float().contiguous(), found["matches0"],
+                                                     counts0=b["counts0"], ransac_thresh=self.val_thresh)
+        return per_pair, found, self.engine.homography_corner_error(H, b["M"], shape)
+
+    def validate(self, epoch):
+        """One pass over val_dataset (see the module docstring) -> dict of the scalars, also written through _scalar under `epoch` and
+        printed on one line: val_loss (sum_b w_b loss_b / max(1, sum_b w_b) over ALL pairs, w_b as in batch_loss), val_precision,
+        val_recall, val_corner_error_median (of the mean corner error per pair, in pixels; a failed fit is +inf and stays in the order
+        statistics: the median of an even count is the mean of the two middle ones), val_homography_correct_1 / _3 / _5 (the share of
+        pairs whose corner error is below that many pixels).  The net is left in the mode it was in."""
+        if self.val_dataset is None:
+            raise RuntimeError("SuperGlueTrainer.validate: no val_dataset")
+        if len(self.val_dataset) == 0:
+            raise RuntimeError("SuperGlueTrainer.validate: the validation set is empty")
+        ds, was_training = self.val_dataset, self.net.training
+        had_seed, old_seed = hasattr(ds, "seed"), getattr(ds, "seed", None)
+        dev = self._device()
+        loss_sum, w_sum = torch.zeros((), dtype=torch.float32, device=dev), torch.zeros((), dtype=torch.float32, device=dev)
+        stats, errors = torch.zeros(3, dtype=torch.int64, device=dev), []
+        self.net.eval()
+        try:
+            if had_seed:
+                ds.seed = self._val_seed
+            with torch.no_grad():
+                for indices in self._val_batches():
+                    b = ds.batch(indices)
+                    per_pair, found, err = self._validate_batch(b)
+                    w = ((b["counts0"] > 0) & (b["counts1"] > 0)).to(per_pair.dtype)
+                    loss_sum, w_sum = loss_sum + (w * per_pair).sum(), w_sum + w.sum()
+                    stats = stats + found["stats"].sum(0)
+                    errors.append(err)
+                err = torch.sort(torch.cat(errors))[0]
+                n = err.numel()
+                lo, hi = err[(n - 1) // 2], err[n // 2]
+                median = torch.where(lo == hi, lo, 0.5 * (lo + hi))          # (inf + inf stays inf; no inf - inf anywhere)
+                row = torch.cat([(loss_sum / w_sum.clamp(min=1.0)).reshape(1).double(), stats.double(), median.reshape(1),
+                                 torch.stack([(err < k).double().mean() for k in (1.0, 3.0, 5.0)])]).cpu().tolist()      # the ONE read-back
+        finally:
+            if had_seed:
+                ds.seed = old_seed
+            self.net.train(was_training)
+        n_gt, n_pred, n_ok = (int(v) for v in row[1:4])
+        out = {"val_loss": row[0], "val_precision": n_ok / max(n_pred, 1), "val_recall": n_ok / max(n_gt, 1), "val_corner_error_median": row[4],
+               "val_homography_correct_1": row[5], "val_homography_correct_3": row[6], "val_homography_correct_5": row[7]}
+        for tag, value in out.items():
+            self._scalar(tag, value, epoch)
+        print("Validation [{}]: ".format(epoch) + ", ".join("{} {:.4f}".format(k, v) for k, v in out.items()))
+        self.last_validation = out
+        return out
+
     # ---------------------------------------------------------------------------------------------- the loop
     def train(self, epochs):
         """superpoint_glue_train.py:101-168 from the epoch after the last finished one to `epochs`: an optional seeded shuffle, batches of
         batch_size with drop_last, 'Mean_Loss' every log_interval steps, 'epoch_loss' and a checkpoint at the end of every epoch.  The
         dataset's warps of an epoch follow from (its seed, the epoch): every epoch sees new warps, a resumed run the ones the
-        uninterrupted run saw.  max_steps > 0 ends the run after that many steps, with a checkpoint of the epoch it stands in."""
+        uninterrupted run saw.  max_steps > 0 ends the run after that many steps, with a checkpoint of the epoch it stands in.  With a
+        validation set, validate(epoch) follows the checkpoint of every val_interval-th epoch."""
         n = len(self.dataset)
         batches = n // self.batch_size
         if batches == 0:
@@ -208,6 +291,8 @@ class SuperGlueTrainer:
             self.epoch = epoch
             where = self.save(epoch)
             print("Epoch [{}/{}] done. Epoch Loss {}. Checkpoint saved to {}".format(epoch, epochs, epoch_loss, where))
+            if self.val_dataset is not None and epoch % self.val_interval == 0:
+                self.validate(epoch)
             if cut:
                 break
         return self.epoch

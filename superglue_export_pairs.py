@@ -50,18 +50,22 @@ def build_parser():
 
 
 class SyntheticPairs(GlueSparse):
-    """the dataset over N synthetic images instead of a directory"""
+    """the dataset over N synthetic images instead of a directory; `first`: the number of its first image (a validation set beside a
+    training set starts where that one ends), `superpoint`: another dataset's SuperPoint to share instead of building one"""
 
-    def __init__(self, n, sp_config, resize, device):
+    def __init__(self, n, sp_config, resize, device, first=0, superpoint=None):
         from image_matching_amd.superpoint.models.superpoint_test import SuperPoint
-        self.device, self.resize = device, resize
-        self.files = [f"synthetic_{i:04d}" for i in range(n)]
+        self.device, self.resize, self.first = device, resize, int(first)
+        self.files = [f"synthetic_{i:04d}" for i in range(self.first, self.first + n)]
+        if superpoint is not None:
+            self.superpoint = superpoint
+            return
         self.superpoint = SuperPoint(sp_config).to(device)
         self.superpoint.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in synth.make_superpoint_state_dict(sp_config['descriptor_dim']).items()})
 
     def _read(self, index):
         from image_matching_amd import trainpairs
-        img = synth.synth_pair(index, self.resize[1], self.resize[0])[0]
+        img = synth.synth_pair(self.first + index, self.resize[1], self.resize[0])[0]
         image = np.clip(np.rint(img.astype(np.float64) * 255.0), 0, 255).astype(np.uint8)
         return image, trainpairs.sample_matrix(np.random.default_rng([self.seed, index]), image.shape[:2])
 

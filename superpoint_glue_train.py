@@ -9,7 +9,11 @@ The flags are the reference's, with its names and defaults and with the types re
 ints, --learning_rate a float, --resume, --shuffle and --show_keypoints booleans (`--resume`, `--resume true`, `--shuffle false`).  The
 checkpoint to resume from is <Result_dir>/<checkpoints_dir>/<checkpoints_name> (the reference's line names an undefined variable).
 Not in the reference: --synthetic N (N synthetic images and synthetic SuperPoint weights, no dataset), --iters K (stop after K steps,
-with a checkpoint), --seed (of the shuffle and of the warps) and --optimizer flat|torch.
+with a checkpoint), --seed (of the shuffle and of the warps), --optimizer flat|torch, and the validation epochs: --val_path DIR (a
+directory of validation images), --val_synthetic N (N synthetic validation images beside --synthetic, other images than the training
+ones) and --val_interval E (validate after every E-th epoch).  A validation prints one line -- loss, precision, recall, the median corner
+error of the homography fitted to the predicted matches and the share of pairs below 1, 3 and 5 px -- and logs the same scalars.  Without
+these flags the script runs as it did.
 
 Scalars go to tensorboardX's SummaryWriter where that package is installed, otherwise to <Result_dir>/logdir/scalars.jsonl.  One GPU."""
 import argparse
@@ -59,6 +63,11 @@ def build_parser():
     parser.add_argument('--iters', type=int, default=0, help='stop after this many optimiser steps, with a checkpoint (0 = run every epoch)')
     parser.add_argument('--seed', type=int, default=0, help='seed of the shuffle and of the warp sampler')
     parser.add_argument('--optimizer', type=str, default='flat', choices=['flat', 'torch'], help='one-launch Adam on a flat arena, or torch.optim.Adam')
+    # the validation epochs: absent from the namespace unless given (validation_options() has the defaults), so that a run without them
+    # sees the options it always saw
+    parser.add_argument('--val_path', type=str, default=argparse.SUPPRESS, help='directory of validation images: a validation after every --val_interval epochs (default: none)')
+    parser.add_argument('--val_interval', type=int, default=argparse.SUPPRESS, help='epochs between two validations (default: 1)')
+    parser.add_argument('--val_synthetic', type=int, default=argparse.SUPPRESS, help='validate on this many synthetic images, with --synthetic (default: 0)')
     return parser
 
 
@@ -70,6 +79,11 @@ def configs(opt):
         'superglue': {'descriptor_dim': opt.descriptor_dim, 'keypoint_encoder': opt.keypoint_encoder,
                       'sinkhorn_iterations': opt.sinkhorn_iterations, 'match_threshold': opt.match_threshold},
     }
+
+
+def validation_options(opt):
+    """(val_path, val_interval, val_synthetic) with their defaults ('', 1, 0)"""
+    return getattr(opt, 'val_path', ''), int(getattr(opt, 'val_interval', 1)), int(getattr(opt, 'val_synthetic', 0))
 
 
 def checkpoint_path(opt):
@@ -98,11 +112,24 @@ def main(argv=None):
     else:
         train_set = GlueSparse(os.path.join(opt.image_path, 'train'), config['superpoint'], opt.resize, device)
     train_set.seed = opt.seed
+    val_set = None
+    val_path, val_interval, val_synthetic = validation_options(opt)
+    if val_interval < 1:
+        raise SystemExit("--val_interval must be at least 1")
+    if val_synthetic > 0:
+        if not synthetic:
+            raise SystemExit("--val_synthetic goes with --synthetic (the synthetic SuperPoint weights)")
+        val_set = SyntheticPairs(val_synthetic, config['superpoint'], opt.resize, device, first=opt.synthetic, superpoint=train_set.superpoint)
+    elif val_path:
+        val_set = GlueSparse.beside(train_set, val_path)
+    if val_set is not None:
+        val_set.seed = opt.seed + 0x5EED      # the warps of every validation, apart from every training epoch's of a run of any usual length
 
     writer = make_writer(opt.Result_dir + '/logdir')
     trainer = SuperGlueTrainer(config['superglue'], train_set, train_set._engine(), optimizer=opt.optimizer, lr=opt.learning_rate,
                                batch_size=opt.batch_size, shuffle=opt.shuffle, seed=opt.seed, result_dir=opt.Result_dir, writer=writer,
-                               show_keypoints=opt.show_keypoints, viz_extension=opt.viz_extension, max_steps=opt.iters)
+                               show_keypoints=opt.show_keypoints, viz_extension=opt.viz_extension, max_steps=opt.iters,
+                               **({} if val_set is None else {"val_dataset": val_set, "val_interval": val_interval}))
 
     if opt.pretrain_weights in ['indoor', 'outdoor']:
         import image_matching_amd
@@ -125,7 +152,8 @@ def main(argv=None):
     writer.close()
     ckpt_dir = os.path.join(opt.Result_dir, 'checkpoints')
     print(json.dumps({"epoch": trainer.epoch, "steps": trainer.steps, "checkpoints": sorted(os.listdir(ckpt_dir)) if os.path.isdir(ckpt_dir) else [],
-                      "last": trainer.history[-1] if trainer.history else None}))
+                      "last": trainer.history[-1] if trainer.history else None,
+                      **({} if val_set is None else {"validation": trainer.last_validation})}))
 
 
 if __name__ == '__main__':
