@@ -170,3 +170,114 @@ def shade_case(ksize, H, W):
     return {'img': rng.integers(0, 256, (B, H, W)).astype(np.uint8), 'ellipses': ell, 'n_ellipses': np.asarray([20, 0, 1, 20], np.int32),
             'taps': np.tile((g / g.sum()).astype(np.float32), (B, 1)), 'ksize': np.full(B, ksize, np.int32),
             'transparency': np.asarray([0.8, 0.5, -0.5, 0.3], np.float32), 'on': np.asarray([1, 1, 1, 0], np.int32)}
+
+
+# ---------------------------------------------------------------------------------------------------------------- workload-size cases
+# (tests/test_gpu_sp_workload_paths.py runs them; tests/test_sp_workload_paths_host.py checks what they promise.)  The lists above stay
+# as they are: host tests and fixtures hang on them.
+
+def gaussian_taps(ksize):
+    """cv2.getGaussianKernel(ksize, 0)'s formula, normalised in float64, as shade_case forms its taps"""
+    sigma = 0.3 * ((ksize - 1) * 0.5 - 1.0) + 0.8
+    x = np.arange(ksize, dtype=np.float64) - (ksize - 1) * 0.5
+    g = np.exp(-(x * x) / (2.0 * sigma * sigma))
+    return (g / g.sum()).astype(np.float32)
+
+
+def _draw_ellipses(rng, H, W, E, draw):
+    """E ellipses from draw(i) -> (cx, cy, ax, ay, degrees); one with a pixel within BOUNDARY_MARGIN of its boundary is drawn again"""
+    ell, i = np.zeros((E, 5), np.float32), 0
+    while i < E:
+        ell[i] = draw(i)
+        i += int(np.abs(ellipse_form(H, W, ell[i]) - 1.0).min() > BOUNDARY_MARGIN)
+    return ell
+
+
+def shade_case_wide(ksize, H, W, first_column=256):
+    """The four images of shade_case -- 20 ellipses, 0 ellipses, one ellipse that covers the image, 20 ellipses with the on/off word
+    clear -- for images wider than one row segment of the row pass and only a few rows high.  shade_case cannot draw those: with
+    min(H, W) / 4 < 2 its integer axes are 0 or 1, and a circle of radius 1 about a lattice point always has pixels on its boundary, so
+    its redraw rule never ends.  Here the axes are real numbers and the centres lie anywhere in the image.  Ellipse 0 of images 0 and 3
+    is small and centred so that every pixel of it lies in a column >= first_column."""
+    rng = np.random.default_rng(2000 + ksize)
+    B, E = 4, 20
+    assert W > first_column
+    ell = np.zeros((B, E, 5), np.float32)
+    far = max(0.95, min(H, W - first_column) / 2.5)
+
+    def draw(i):
+        if i == 0:                                                  # a radius below 1 about a lattice point: that pixel alone
+            ax, ay = rng.uniform(0.6, far, 2)
+            r = int(max(ax, ay))
+            return rng.integers(first_column + r, W - r), rng.integers(0, H), ax, ay, rng.random() * 90
+        ax, ay = rng.uniform(0.6, max(H, W) / 32, 2)
+        return rng.integers(0, W), rng.integers(0, H), ax, ay, rng.random() * 90
+    for b in (0, 3):
+        ell[b] = _draw_ellipses(rng, H, W, E, draw)
+    ell[2, 0] = (W / 2, H / 2, H + W, H + W, 30.0)
+    return {'img': rng.integers(1, 256, (B, H, W)).astype(np.uint8), 'ellipses': ell, 'n_ellipses': np.asarray([20, 0, 1, 20], np.int32),
+            'taps': np.tile(gaussian_taps(ksize), (B, 1)), 'ksize': np.full(B, ksize, np.int32),
+            'transparency': np.asarray([0.8, 0.5, -0.5, 0.3], np.float32), 'on': np.asarray([1, 1, 1, 0], np.int32)}
+
+
+SHADE_BATCH_KSIZES = (3, 51, 101)
+
+
+def shade_batch_case(B, H, W, off=(), empty=()):
+    """B images for one imx_photo_shade call: ksize cycles through SHADE_BATCH_KSIZES (neighbours always differ, and an image's ksize
+    differs from that of the image 64 or 128 places before it), the taps beyond an image's ksize are NaN (never read), 20 ellipses drawn
+    as shade_case draws them, transparency in +-[0.2, 0.8]; the images `off` have the on/off word clear, the images `empty` 0 ellipses."""
+    rng = np.random.default_rng(3000 + B)
+    E, kcap = 20, max(SHADE_BATCH_KSIZES)
+    min_dim = min(H, W) / 4
+    ell = np.zeros((B, E, 5), np.float32)
+
+    def draw(i):
+        ax, ay = (int(max(rng.random() * min_dim, min_dim / 5)) for _ in range(2))
+        r = max(ax, ay)
+        return rng.integers(r, W - r), rng.integers(r, H - r), ax, ay, rng.random() * 90
+    ksize = np.asarray([SHADE_BATCH_KSIZES[b % 3] for b in range(B)], np.int32)
+    taps = np.full((B, kcap), np.nan, np.float32)
+    for b in range(B):
+        ell[b] = _draw_ellipses(rng, H, W, E, draw)
+        taps[b, :ksize[b]] = gaussian_taps(int(ksize[b]))
+    n_ell, on = np.full(B, E, np.int32), np.ones(B, np.int32)
+    n_ell[list(empty)], on[list(off)] = 0, 0
+    return {'img': rng.integers(1, 256, (B, H, W)).astype(np.uint8), 'ellipses': ell, 'n_ellipses': n_ell, 'taps': taps, 'ksize': ksize,
+            'transparency': (rng.uniform(0.2, 0.8, B) * rng.choice([-1.0, 1.0], B)).astype(np.float32), 'on': on}
+
+
+def shade_one(c, b, dtype=np.float64):
+    """image b of a shade case through shade (float64) or shade_f32"""
+    fn = shade if dtype == np.float64 else shade_f32
+    return fn(c['img'][b], c['ellipses'][b, :c['n_ellipses'][b]], c['taps'][b, :c['ksize'][b]], c['transparency'][b], bool(c['on'][b]))
+
+
+def _fma32(a, b, c):
+    """round32(a b + c) of float32 arrays: the product is exact in float64"""
+    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
+
+
+def shade_f32(a_u8, ellipses, taps, transparency, on=True):
+    """imx_photo_shade for one image in the float32 order DESIGN.md section 21 states: the mask decided in float64, each blur pass one
+    fused multiply-add per tap from +0 with the taps ascending, rows before columns, then 1 - t m / 255 and the product, the clamp and
+    the division by 255, each operation rounded to float32 on its own"""
+    f = np.float32
+    a = a_u8.astype(f)
+    if not on:
+        return a / f(255)
+    H, W = a.shape
+    t = np.asarray(taps, f)
+    k = len(t)
+    m = shade_mask(H, W, ellipses).astype(f)
+    cols = reflect101(np.arange(W)[:, None] + np.arange(k)[None] - k // 2, W)
+    rows = reflect101(np.arange(H)[:, None] + np.arange(k)[None] - k // 2, H)
+    r = np.zeros((H, W), f)
+    for j in range(k):
+        r = _fma32(np.broadcast_to(t[j], (H, W)), m[:, cols[:, j]], r)
+    s = np.zeros((H, W), f)
+    for j in range(k):
+        s = _fma32(np.broadcast_to(t[j], (H, W)), r[rows[:, j], :], s)
+    v = (a / f(255)) * f(255)
+    scale = f(1) - (f(transparency) * s) / f(255)
+    return np.clip(v * scale, f(0), f(255)) / f(255)

@@ -185,3 +185,78 @@ def desc_loss(desc_a, desc_b, pair_a, pair_b, choice, nonmatch_b, lamda_d=250., 
     hard = int((v != 0).sum())
     non = v.sum() / (hard + 1)                                                              # sparse_loss.py:88-96
     return float(lamda_d * match + non), float(lamda_d * match), float(non), hard, prod.numpy()
+
+
+# ---------------------------------------------------------------------------------------------- workload-size cases
+# (tests/test_gpu_sp_workload_paths.py runs them, for imx_warp_labels and -- through tests/sploop_ref.py -- imx_warp_labels_bi;
+# tests/test_sp_workload_paths_host.py checks what they promise)
+def workload_mats(B):
+    """mild pixel-space homographies, one per image: a shrink of about 3 %, a small shear, a shift of a few pixels and a perspective
+    term of 1e-5 -- every pixel of an image of up to 900 x 900 stays inside it, and neighbouring integer points now and then round to
+    the same pixel"""
+    return np.stack([np.array([[0.97 - 0.004 * b, 0.012, 4.25 + b], [-0.009, 0.968 + 0.003 * b, 8.5], [1.5e-5, -1e-5, 1.0]], F32) for b in range(B)])
+
+
+def warped_pixels(m, x, y):
+    """the pixel (px, py) warpLabels writes for the integer points (x, y): warp_points, then round() half to even"""
+    wx, wy = warp_points(m, np.asarray(x, F32), np.asarray(y, F32))
+    return np.rint(wx).astype(np.int64), np.rint(wy).astype(np.int64)
+
+
+CLUSTER = ((10, 200, -1), (5, 100))      # the point indices of a case's triple (the last is the image's last point) and of its pair
+
+
+def workload_points(H, W, counts, row0, seed, avoid=None, low=150):
+    """(pts_rows, mats): counts[b] points (x, y) with fractional parts for image b under workload_mats.  Per image: the points
+    CLUSTER[0] are the integer points (x, y), (x + 1, y), (x, y + 1) of a place where all three round to ONE pixel of a row >= row0, the
+    points CLUSTER[1] are (x, y), (x + 1, y) of another such place; the first `low` of the others have y so large that they land in
+    rows >= row0; the rest lie anywhere.  `avoid` (B,H,W) bool: no point lands within two pixels of a pixel set there."""
+    rng = np.random.default_rng(seed)
+    B = len(counts)
+    mats = workload_mats(B)
+    near = np.zeros((B, H + 4, W + 4), bool)
+    if avoid is not None:
+        for dy in range(5):
+            for dx in range(5):
+                near[:, dy:dy + H, dx:dx + W] |= avoid
+    near = near[:, 2:-2, 2:-2]
+    ys, xs = (g.reshape(-1) for g in np.mgrid[0:H - 1, 0:W - 1])
+    out = []
+    for b, n in enumerate(counts):
+        m = mats[b]
+        (px0, py0), (px1, py1), (px2, py2) = warped_pixels(m, xs, ys), warped_pixels(m, xs + 1, ys), warped_pixels(m, xs, ys + 1)
+        assert px0.min() >= 0 and px0.max() < W and py0.min() >= 0 and py0.max() < H
+        same_x, same_y = (px0 == px1) & (py0 == py1), (px0 == px2) & (py0 == py2)
+        ok = (py0 >= row0 + 8) & ~near[b, py0, px0]
+        t = rng.choice(np.flatnonzero(same_x & same_y & ok))
+        p = rng.choice(np.flatnonzero(same_x & ~same_y & ok & (np.abs(ys - ys[t]) > 8)))
+        pts = np.zeros((n, 2), np.int64)
+        i3, i2 = [i % n for i in CLUSTER[0]], list(CLUSTER[1])
+        pts[i3] = [(xs[t], ys[t]), (xs[t] + 1, ys[t]), (xs[t], ys[t] + 1)]
+        pts[i2] = [(xs[p], ys[p]), (xs[p] + 1, ys[p])]
+        taken = {tuple(q) for q in pts[i3 + i2]}
+        y_low = int(row0 / 0.95) + 12
+        for k, i in enumerate(j for j in range(n) if j not in i3 + i2):
+            while True:
+                q = (int(rng.integers(0, W)), int(rng.integers(y_low if k < low else 0, H)))
+                qx, qy = warped_pixels(m, [q[0]], [q[1]])
+                if q not in taken and not near[b, qy[0], qx[0]]:
+                    break
+            taken.add(q)
+            pts[i] = q
+        out.append((pts + rng.uniform(0.05, 0.95, (n, 2))).astype(F32))
+    return out, mats
+
+
+def det_case(B, H, W, seed):
+    """(semi (B,65,H/8,W/8) of N(0, 3^2) logits, labels (B,H,W) of density 0.01)"""
+    rng = np.random.default_rng(seed)
+    semi = rng.standard_normal((B, 65, H // 8, W // 8), dtype=F32) * F32(3)
+    return semi, (rng.random((B, H, W), dtype=F32) < 0.01).astype(F32)
+
+
+def last_cells_mask(B, H, W, n):
+    """(B,H,W): 1 on the pixels of the last n 8x8 cells in (image, cell row, cell column) order, 0 elsewhere"""
+    cm = np.zeros(B * (H // 8) * (W // 8), F32)
+    cm[-n:] = 1
+    return np.ascontiguousarray(np.broadcast_to(cm.reshape(B, H // 8, 1, W // 8, 1), (B, H // 8, 8, W // 8, 8))).reshape(B, H, W)
