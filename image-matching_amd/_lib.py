@@ -1,7 +1,7 @@
 """ctypes binding of libimx.so (C ABI: include/imx.h), libimx_train.so (include/imx_train.h), libimx_sgtrain.so
 (include/imx_sgtrain.h), libimx_spnet.so (include/imx_spnet.h), libimx_spnorm.so (include/imx_spnorm.h), libimx_sppool.so (include/imx_sppool.h),
-libimx_photo.so (include/imx_photo.h), libimx_sploop.so (include/imx_sploop.h), libimx_sgloop.so (include/imx_sgloop.h) and libimx_homog.so
-(include/imx_homog.h).  There is no CPU fallback: if the library is missing or no GPU is present the product path raises."""
+libimx_photo.so (include/imx_photo.h), libimx_sploop.so (include/imx_sploop.h), libimx_sgloop.so (include/imx_sgloop.h), libimx_homog.so
+(include/imx_homog.h) and libimx_speval.so (include/imx_speval.h): eleven libraries.  There is no CPU fallback: if the library is missing or no GPU is present the product path raises."""
 import ctypes
 import os
 
@@ -143,6 +143,15 @@ _HOMOG_ARGTYPES = {
 }
 HOMOG_EXPORTS = tuple(_HOMOG_ARGTYPES)
 
+# libimx_speval.so (C ABI: include/imx_speval.h): the mutual nearest-neighbour descriptor matcher and the pair metrics of SuperPoint's validation
+# under a known warp, on libimx.so's handles -- a library of its own because the other ten symbol tables are pinned to their headers; name -> argtypes
+SPEVAL_LIB_PATH = os.path.join(_HERE, "libimx_speval.so")
+_SPEVAL_ARGTYPES = {
+    "imx_mutual_nn_match": [_vp, _i32, _i32, _vp, _i64, _i64, _i64, _vp, _i32, _vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
+    "imx_keypoint_pair_metrics": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f64, _vp, _vp, _vp],
+}
+SPEVAL_EXPORTS = tuple(_SPEVAL_ARGTYPES)
+
 _lib = None
 _train = None
 _sgtrain = None
@@ -153,6 +162,7 @@ _photo = None
 _sploop = None
 _sgloop = None
 _homog = None
+_speval = None
 
 
 def load_library():
@@ -349,4 +359,19 @@ def load_homog_library():
     for name, argtypes in _HOMOG_ARGTYPES.items():
         getattr(lib, name).argtypes = argtypes          # raises AttributeError if a declared symbol is missing
     _homog = lib
+    return lib
+
+
+def load_speval_library():
+    """Load libimx_speval.so (built beside libimx.so by the same make); libimx.so is loaded first: it makes the handles."""
+    global _speval
+    if _speval is not None:
+        return _speval
+    load_library()
+    if not os.path.exists(SPEVAL_LIB_PATH):
+        raise RuntimeError(f"libimx_speval.so not found at {SPEVAL_LIB_PATH}: build it with `make -C image-matching_amd/csrc`")
+    lib = ctypes.CDLL(SPEVAL_LIB_PATH)
+    for name, argtypes in _SPEVAL_ARGTYPES.items():
+        getattr(lib, name).argtypes = argtypes          # raises AttributeError if a declared symbol is missing
+    _speval = lib
     return lib

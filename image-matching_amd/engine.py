@@ -53,6 +53,7 @@ class Engine:
         self.sploop = L.load_sploop_library()      # the soft labels and the optimiser step of the training loop (include/imx_sploop.h), likewise
         self.sgloop = L.load_sgloop_library()      # the matches of SuperGlue's training forward from the loss's Sinkhorn (include/imx_sgloop.h), likewise
         self.homog = L.load_homog_library()        # the RANSAC homography fit and the corner error (include/imx_homog.h), likewise
+        self.speval = L.load_speval_library()      # the mutual nearest-neighbour matcher and the pair metrics (include/imx_speval.h), likewise
         if not torch.cuda.is_available():
             raise ImxError("image_matching_amd needs a ROCm GPU (torch.cuda.is_available() is False); "
                            "there is no CPU fallback on the product path")
@@ -327,6 +328,79 @@ class Engine:
         err = torch.empty(B, dtype=torch.float64, device=dev)
         self._check(self.homog.imx_homography_corner_error(self.handle, _ptr(H), _ptr(gt), B, width, height, _ptr(err), _stream(dev)))
         return err
+
+    def mutual_nn_match(self, desc0, desc1, n0=None, n1=None):
+        """Mutual nearest neighbours by inner product -- for unit-norm descriptors the brute-force L2 matcher with cross-check of the
+        SuperPoint paper's protocol (include/imx_speval.h).  desc{0,1}: (B,d,N) float32 tensors on the device, any strides (a transposed
+        view of superpoint_batch's (B,K,d) is read in place); d is the tensors' own, not the configured descriptor_dim.  n0, n1: (B)
+        int32 counts or None.  Returns matches0 (B,N0), matches1 (B,N1) int64 (-1 = no mutual neighbour) and sim0 (B,N0), sim1 (B,N1),
+        the best similarity of every row, mutual or not.  The similarity matrix is never stored.  No host synchronisation."""
+        who, dev = "mutual_nn_match", self.device
+        for name, t in (("desc0", desc0), ("desc1", desc1)):
+            if not isinstance(t, torch.Tensor) or t.device != dev:
+                raise ImxError(f"{who}: {name} must be a tensor on {dev}, got {getattr(t, 'device', type(t))}")
+            if t.dtype != torch.float32 or t.dim() != 3:
+                raise ImxError(f"{who}: {name} must be (B,d,N) float32, got {tuple(t.shape)} {t.dtype}")
+        if desc0.shape[0] != desc1.shape[0] or desc0.shape[1] != desc1.shape[1]:
+            raise ImxError(f"{who}: the two sides differ in batch size or descriptor dim: {tuple(desc0.shape)} and {tuple(desc1.shape)}")
+        B, D, N0 = (int(v) for v in desc0.shape)
+        N1 = int(desc1.shape[2])
+        if B < 1 or N0 < 1 or N1 < 1 or not 1 <= D <= 1024:
+            raise ImxError(f"{who}: bad shape B={B} d={D} N0={N0} N1={N1} (B, N0, N1 >= 1, 1 <= d <= 1024)")
+        for n in (n0, n1):
+            if n is not None and not (isinstance(n, torch.Tensor) and n.dtype == torch.int32 and n.dim() == 1 and n.numel() == B
+                                      and n.device == dev and n.is_contiguous()):
+                raise ImxError(f"{who}: counts must be contiguous int32 tensors of {B} elements on {dev}")
+        m0 = torch.empty(B, N0, dtype=torch.int64, device=dev)
+        m1 = torch.empty(B, N1, dtype=torch.int64, device=dev)
+        sim0 = torch.empty(B, N0, dtype=torch.float32, device=dev)
+        sim1 = torch.empty(B, N1, dtype=torch.float32, device=dev)
+        s0, s1 = desc0.stride(), desc1.stride()
+        self._check(self.speval.imx_mutual_nn_match(self.handle, B, D, _ptr(desc0), s0[0], s0[1], s0[2], _ptr(n0), N0,
+                                                    _ptr(desc1), s1[0], s1[1], s1[2], _ptr(n1), N1,
+                                                    _ptr(m0), _ptr(m1), _ptr(sim0), _ptr(sim1), _stream(dev)))
+        return m0, m1, sim0, sim1
+
+    def keypoint_pair_metrics(self, kpts0, n0, kpts1, n1, H_gt, size_hw, eps=3.0, matches0=None):
+        """The pair metrics of a detector under known warps (include/imx_speval.h): kpts0 (B,K0,2), kpts1 (B,K1,2) float32 (x, y), n0,
+        n1 (B) int32 counts or None, H_gt (B,3,3) float64 on pixel coordinates mapping image 0 to image 1, size_hw = (height, width),
+        matches0 (B,K0) int64 or None.  Returns counts (B,8) int32 = [v0, v1, r0, r1, m, c, bad, 0] and sums (B,2) float64: the points in
+        the shared view, the repeated ones (a visible point of the other side within eps after warping), the matches and the correct
+        ones, whether H_gt was singular, and the sums of the nearest distances of the repeated points.  K0, K1 <= 4096.  No host
+        synchronisation."""
+        who, dev = "keypoint_pair_metrics", self.device
+        tensors = [("kpts0", kpts0), ("kpts1", kpts1), ("H_gt", H_gt)] + ([("matches0", matches0)] if matches0 is not None else [])
+        for name, t in tensors:
+            if not isinstance(t, torch.Tensor) or t.device != dev:
+                raise ImxError(f"{who}: {name} must be a tensor on {dev}, got {getattr(t, 'device', type(t))}")
+        if kpts0.dtype != torch.float32 or kpts1.dtype != torch.float32:
+            raise ImxError(f"{who}: keypoints must be float32, got {kpts0.dtype} and {kpts1.dtype}")
+        if kpts0.dim() != 3 or kpts1.dim() != 3 or kpts0.shape[2] != 2 or kpts1.shape[2] != 2 or kpts0.shape[0] != kpts1.shape[0]:
+            raise ImxError(f"{who}: expected kpts0 (B,K0,2) and kpts1 (B,K1,2), got {tuple(kpts0.shape)} and {tuple(kpts1.shape)}")
+        B, K0, K1 = int(kpts0.shape[0]), int(kpts0.shape[1]), int(kpts1.shape[1])
+        if B < 1 or K0 < 1 or K1 < 1:
+            raise ImxError(f"{who}: empty input B={B} K0={K0} K1={K1}")
+        if H_gt.dtype != torch.float64 or tuple(H_gt.shape) != (B, 3, 3):
+            raise ImxError(f"{who}: H_gt must be ({B},3,3) float64, got {tuple(H_gt.shape)} {H_gt.dtype}")
+        if matches0 is not None and (matches0.dtype != torch.int64 or tuple(matches0.shape) != (B, K0)):
+            raise ImxError(f"{who}: matches0 must be ({B},{K0}) int64, got {tuple(matches0.shape)} {matches0.dtype}")
+        for n in (n0, n1):
+            if n is not None and not (isinstance(n, torch.Tensor) and n.dtype == torch.int32 and n.dim() == 1 and n.numel() == B
+                                      and n.device == dev and n.is_contiguous()):
+                raise ImxError(f"{who}: counts must be contiguous int32 tensors of {B} elements on {dev}")
+        height, width = (int(v) for v in size_hw)
+        if height < 1 or width < 1:
+            raise ImxError(f"{who}: bad image size {size_hw!r}")
+        e = float(eps)
+        if not (e >= 0.0 and math.isfinite(e)):
+            raise ImxError(f"{who}: eps must be non-negative and finite, got {eps!r}")
+        kpts0, kpts1, H_gt = kpts0.contiguous(), kpts1.contiguous(), H_gt.contiguous()
+        matches0 = matches0.contiguous() if matches0 is not None else None
+        counts = torch.empty(B, 8, dtype=torch.int32, device=dev)
+        sums = torch.empty(B, 2, dtype=torch.float64, device=dev)
+        self._check(self.speval.imx_keypoint_pair_metrics(self.handle, _ptr(kpts0), _ptr(n0), _ptr(kpts1), _ptr(n1), _ptr(matches0), _ptr(H_gt),
+                                                          B, K0, K1, width, height, e, _ptr(counts), _ptr(sums), _stream(dev)))
+        return counts, sums
 
     def knn_ratio_match(self, desc0, desc1, ratio=0.7, n0=None, n1=None):
         """Exact 2-NN + ratio test (superpoint_flann_test.py:66-74 without FLANN's approximation).

@@ -8,6 +8,13 @@ sparse descriptor loss, value and gradient in the library) on the `*_gaussian` l
 (Train_model_heatmap.py:135-142), backward(), FlatAdam.step() (one launch, which zeroes the gradients too).  Nothing inside a step
 waits for the device; scalars are read back every tensorboard_interval steps and on validation only.
 
+With the top-level config key `validation_metrics: {enable: true, pairs: 16, max_keypoints: 1000, eps: 3, keep_best: true}` train() also
+calls validate_metrics() at every validation_interval, after the checkpoint of that iteration and after the loss validation: what the
+DEPLOYED network would do from the present weights (superpoint/validation.py: repeatability, localisation error, matching score,
+homography correctness), as one ("metrics", n_iter, {...}) row of `history`, and with keep_best a superPointNet_best_checkpoint.pth.tar
+whenever val_homography_correct_3 improves (ties: val_repeatability).  It acts on a copy of the state dict and leaves the network, the
+optimiser, the loaders' datasets' seeds and every generator as they were.  Absent or off: nothing changes.
+
 ONE GPU: dataParallel() keeps the single-device model and says so.  Not served, raising as in the base class: detector_loss 'l2',
 dense_loss; add_res_loss / pred_soft_argmax and a subpixel head raise here; images and histograms are not written to the writer."""
 import copy
@@ -25,6 +32,8 @@ from ..sptrain_model import SuperPointTrainable
 from .Train_model_heatmap import Train_model_heatmap as _ForwardOnly
 
 SCALAR_KEYS = ("loss", "loss_det", "loss_det_warp", "positive_dist", "negative_dist")
+METRICS_DEFAULT = {"enable": False, "pairs": 16, "max_keypoints": 1000, "eps": 3, "keep_best": True}
+BEST_NAME = "superPointNet_best_checkpoint.pth.tar"
 
 
 class BatchLoader:
@@ -92,6 +101,9 @@ class Train_model_heatmap(_ForwardOnly):
         self.train_loader = self.val_loader = None
         self._data_seed = None
         self.history = []                 # (task, n_iter, {scalar: float}) of every read-back
+        self.metrics_config = dict(METRICS_DEFAULT, **(config.get("validation_metrics") or {}))
+        self.validator = None             # superpoint/validation.py's, made at the first validate_metrics()
+        self.best = None                  # (val_homography_correct_3, val_repeatability) of the best checkpoint written so far
 
     # ---------------------------------------------------------------------------------------------- model and optimiser
     def loadModel(self, state_dict=None):
@@ -227,17 +239,54 @@ class Train_model_heatmap(_ForwardOnly):
                 if self.n_iter % int(self.config["save_interval"]) == 0:
                     logging.info("save model: every %d interval, current iteration: %d", int(self.config["save_interval"]), self.n_iter)
                     self.saveModel()
+                if self.metrics_config["enable"] and self.n_iter % int(self.config["validation_interval"]) == 0:
+                    self.validate_metrics()
                 if self.n_iter >= self.max_iter:       # (the reference tests > and so runs one step past train_iter; this loop stops at it)
                     logging.info("End training: %d", self.n_iter)
                     break
             if steps == 0:
                 raise RuntimeError("train(): the train loader is empty")
 
-    def saveModel(self):
-        """Train_model_frontend.py:340-353 with save_checkpoint's file name (utils/utils.py:534-541)"""
+    # ---------------------------------------------------------------------------------------------- the deployed network's metrics
+    def validate_metrics(self):
+        """One pass of superpoint/validation.py's SuperPointValidator over the first `pairs` samples of the validation set, on a COPY of
+        the present state dict: the scalars to the writer, one ("metrics", n_iter, row) to history, and with keep_best the best
+        checkpoint.  Returns the row."""
+        from .validation import SuperPointValidator
+        if self.net is None:
+            self.loadModel()
+        m = self.metrics_config
+        if self.validator is None:
+            loader = self.val_loader if self.val_loader is not None else self.train_loader
+            if loader is None:
+                raise RuntimeError("validate_metrics(): set val_loader (or train_loader) first")
+            self.validator = SuperPointValidator(self.config, loader.dataset, self.device, max_keypoints=int(m["max_keypoints"]), eps=float(m["eps"]),
+                                                 pairs=int(m["pairs"]), batch_size=getattr(loader, "batch_size", None), seed=self.seed)
+            best_path = os.path.join(str(self.save_path), BEST_NAME)
+            if m["keep_best"] and not self.config.get("retrain", True) and os.path.exists(best_path):      # a resumed run: the incumbent
+                kept = torch.load(best_path, map_location="cpu").get("metrics") or {}
+                if "val_homography_correct_3" in kept and "val_repeatability" in kept:
+                    self.best = (float(kept["val_homography_correct_3"]), float(kept["val_repeatability"]))
+        state = {k: v.detach().clone() for k, v in self.net.state_dict().items()}
+        row = self.validator.evaluate(state)
+        self.history.append(("metrics", int(self.n_iter), row))
+        logging.info("metrics iter %d: %s", self.n_iter, ", ".join(f"{k}: {v:.4f}" for k, v in row.items()))
+        if self.writer is not None:
+            for k, v in row.items():
+                self.writer.add_scalar(k, v, self.n_iter)
+        key = (row["val_homography_correct_3"], row["val_repeatability"])
+        if m["keep_best"] and (self.best is None or key > self.best):
+            self.best = key
+            self.saveModel(BEST_NAME, metrics=row)
+        return row
+
+    def saveModel(self, name=None, **extra):
+        """Train_model_frontend.py:340-353 with save_checkpoint's file name (utils/utils.py:534-541); `name` and further keys are the
+        best checkpoint's (validate_metrics)"""
         state = {"n_iter": self.n_iter + 1, "model_state_dict": self.net.state_dict(), "optimizer_state_dict": self.optimizer.state_dict(),
                  "loss": self.loss}
-        name = "{}_{}_{}".format("superPointNet", str(self.n_iter), "checkpoint.pth.tar")
+        state.update(extra)
+        name = name or "{}_{}_{}".format("superPointNet", str(self.n_iter), "checkpoint.pth.tar")
         os.makedirs(str(self.save_path), exist_ok=True)
         torch.save(state, os.path.join(str(self.save_path), name))
         logging.info("save checkpoint to %s", name)

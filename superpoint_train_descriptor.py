@@ -2,7 +2,9 @@
 (superpoint/configs/superpoint_allss_train_heatmap.yaml: photometric augmentation, soft `gaussian_label` targets, warped pairs, sparse
 descriptor loss) through datasets/ALLSS_train.py and superpoint/Train_model_heatmap_loop.py to checkpoints in the reference's layout.
 The script's three flags, plus --synthetic N, which needs no dataset (N synthetic images whose pseudo-labels come from homographic
-adaptation on a synthetic-weight network), --size and --iters K (train_iter; the intervals are cut to fit).
+adaptation on a synthetic-weight network), --size, --iters K (train_iter; the intervals are cut to fit) and --val_metrics (at every
+validation_interval: repeatability, localisation error, matching score and homography correctness of the deployed network, and a best
+checkpoint; the config's validation_metrics key with enable set).
 
     python superpoint_train_descriptor.py --synthetic 4 --iters 6 --config tests/golden/superpoint_allss_train_heatmap.yaml
 
@@ -27,6 +29,7 @@ if __name__ == '__main__':
     parser.add_argument("--synthetic", type=int, default=0, help="train on N synthetic images instead of datasets/ALLSS/train")
     parser.add_argument("--size", type=int, nargs=2, default=None, help="H W of the synthetic images (default: 120 160)")
     parser.add_argument("--iters", type=int, default=0, help="train_iter; validation, save and tensorboard intervals are cut to at most half of it")
+    parser.add_argument("--val_metrics", action="store_true", help="validation_metrics.enable: measure the deployed network at every validation_interval")
     args = parser.parse_args()
 
     import yaml
@@ -46,6 +49,8 @@ if __name__ == '__main__':
         config['train_iter'] = args.iters
         for k in ('validation_interval', 'save_interval', 'tensorboard_interval'):
             config[k] = max(1, min(int(config[k]), args.iters // 2))
+    if args.val_metrics:
+        config['validation_metrics'] = dict(config.get('validation_metrics') or {}, enable=True)
     with open(os.path.join(output_dir, 'config.yml'), 'w') as f:
         yaml.dump(config, f, default_flow_style=False)
 
