@@ -230,7 +230,7 @@ int sg_forward(imx_handle_t h, int B, const SgSide sd[2], int64_t* m0, int64_t* 
   const int R = B * (N0p + N1p);
   const size_t off1 = (size_t)B * N0p;   // first row of side 1
   int maxw = d;
-  for (int i = 0; i < c.kenc_n; ++i) maxw = std::max(maxw, c.kenc_channels[i]);
+  for (int i = 0; i < c.kenc_n; ++i) maxw = std::max(maxw, pad32(c.kenc_channels[i]));      // (as finalize_superglue pads the widths)
   WS(x, float, "sg.x", (size_t)R * d * f);
   WS(ta, float, "sg.ta", (size_t)R * maxw * f);
   WS(tb, float, "sg.tb", (size_t)R * maxw * f);
@@ -361,8 +361,15 @@ int sg_forward(imx_handle_t h, int B, const SgSide sd[2], int64_t* m0, int64_t* 
                max0, idx0, max1, idx1, m0, m1, ms0, ms1};
   RUN("matches", launch_matches(ma, s));
   tap(h, "x", x, {R, d});
-  tap(h, "qkv", qkv, {R, 3 * d});                                           // the LAST layer's q|k|v ...
-  if (amax) tap(h, "amax", amax + 8 * (size_t)B * (h->layers.size() - 1), {2 * B, 4});      // ... and its maxima (bit patterns; fetched as floats)
+  if (nl) {
+    tap(h, "qkv", qkv, {R, 3 * d});                                         // the LAST layer's q|k|v ...
+    if (amax) tap(h, "amax", amax + 8 * (size_t)B * (nl - 1), {2 * B, 4});  // ... and its maxima (bit patterns; fetched as floats)
+  } else {
+    // no GNN layers: nothing wrote sg.qkv in this forward and the table has no layer to point at (nl - 1 would wrap): withdrawn, like
+    // "ha_mask" in imx_api.cpp, so that imx_debug_fetch refuses them instead of handing out an earlier forward's or reading wild
+    h->taps.erase("qkv");
+    h->taps.erase("amax");
+  }
   tap(h, "mdesc", mdesc, {R, d});
   tap(h, "scores_in", S, {B, N0p, N1p});
   tap(h, "u", u, {B, N0p + 1});

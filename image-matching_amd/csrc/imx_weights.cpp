@@ -207,12 +207,13 @@ std::vector<float> split_f16x2(const std::vector<float>& w, int K, int N, int Np
   return as_float_words(pl);
 }
 
+// (stat_N: the columns that enter the spread statistic of the fp16 planes where fewer than N are real -- zero-padded widths)
 int upload_gemm(imx_handle_t h, GemmW& out, const std::vector<float>& w, const std::vector<float>& b, int K, int N, int Npad,
-                const char* what) {
+                const char* what, int stat_N = -1) {
   out.w = upload(h, w);
   out.wf = (K % 16 == 0 && K <= 512 && N == Npad) ? upload(h, fragment_order(w, K, Npad)) : nullptr;
   out.wx3 = upload(h, split_bf16x3(w, K, Npad));
-  if (K % 32 == 0 && Npad % 64 == 0) out.wh2 = upload(h, split_f16x2(w, K, N, Npad, &out.wh2_inv, &out.wh2_spread));
+  if (K % 32 == 0 && Npad % 64 == 0) out.wh2 = upload(h, split_f16x2(w, K, stat_N > 0 ? stat_N : N, Npad, &out.wh2_inv, &out.wh2_spread));
   out.b = upload(h, b);
   out.K = K;
   out.N = N;
@@ -290,15 +291,20 @@ int finalize_superglue(imx_handle_t h) {
   for (int i = 0; i < c.kenc_n; ++i) ch.push_back(c.kenc_channels[i]);
   ch.push_back(d);
   for (size_t i = 1; i < ch.size(); ++i)
-    if (ch[i] % 32) return fail(h, "keypoint_encoder widths must be multiples of 32 (got %d)", ch[i]);
+    if (ch[i] < 1) return fail(h, "keypoint_encoder widths must be positive (got %d)", ch[i]);
+  // The kernels take widths that are multiples of 32.  Any other width (the reference accepts every positive one) is padded with
+  // channels whose folded weights and biases are zero: they stay 0 through the ReLU and meet zero rows of the next layer's matrix,
+  // so every sum of the layer gains exact zeros only.
+  std::vector<int> cp(ch);
+  for (size_t i = 1; i < cp.size(); ++i) cp[i] = (ch[i] + 31) / 32 * 32;
   // layer 0: (C1,3,1) + BN -> w[3][C1]
   {
-    const int C1 = ch[1];
+    const int C1 = cp[1];
     std::vector<double> s, t;
-    fold_bn(raw, "kenc.encoder.0", ch.size() > 2 ? "kenc.encoder.1" : "", C1, s, t);
+    fold_bn(raw, "kenc.encoder.0", ch.size() > 2 ? "kenc.encoder.1" : "", ch[1], s, t);
     const auto& src = raw.at("kenc.encoder.0.weight").data;
-    std::vector<float> w(3 * C1), b(C1);
-    for (int n = 0; n < C1; ++n) {
+    std::vector<float> w(3 * C1, 0.f), b(C1, 0.f);
+    for (int n = 0; n < ch[1]; ++n) {
       for (int k = 0; k < 3; ++k) w[k * C1 + n] = (float)((double)src[n * 3 + k] * s[n]);
       b[n] = (float)t[n];
     }
@@ -311,9 +317,12 @@ int finalize_superglue(imx_handle_t h) {
   for (size_t i = 2; i < ch.size(); ++i) {
     int j = 3 * (int)(i - 1);
     GemmW g;
-    if (make_gemm(h, g, raw, "kenc.encoder." + std::to_string(j),
-                  i + 1 < ch.size() ? "kenc.encoder." + std::to_string(j + 1) : "", ch[i - 1], ch[i]))
-      return -1;
+    const std::string conv = "kenc.encoder." + std::to_string(j);
+    std::vector<float> w, b;
+    int Npad = 0;
+    build_gemm_host(raw, conv, i + 1 < ch.size() ? "kenc.encoder." + std::to_string(j + 1) : "", ch[i - 1], ch[i], nullptr, w, b, Npad);
+    w.resize((size_t)cp[i - 1] * Npad, 0.f);      // (rows of the padded input channels; the padded output columns are zero already)
+    if (upload_gemm(h, g, w, b, cp[i - 1], cp[i], Npad, conv.c_str(), ch[i])) return -1;
     h->kenc.push_back(g);
   }
   // channel permutation: reference channel c = dim*HEADS + head (view(b, dim, heads, n),

@@ -697,8 +697,9 @@ __global__ __launch_bounds__(256) void match_finalize(MatchArgs a) {
     long mi = -1;
     float ms = 0.f;
     if (!empty && t < m) {
+      // (a row whose every Z is NaN or -inf -- non-finite descriptors in a valid row -- keeps match_rowmax's sentinel index: no partner)
       const int j = idx0[t];
-      const bool mutual = idx1[j] == t;                                                // (:270)
+      const bool mutual = (unsigned)j < (unsigned)n && idx1[j] == t;                   // (:270)
       ms = mutual ? expf(max0[t]) : 0.f;                                               // (:273)
       if (mutual && ms > a.threshold) mi = j;                                          // (:275,277)
     }
@@ -710,7 +711,7 @@ __global__ __launch_bounds__(256) void match_finalize(MatchArgs a) {
     float ms = 0.f;
     if (!empty && t < n) {
       const int i = idx1[t];
-      const bool mutual = idx0[i] == t;                                                // (:271)
+      const bool mutual = (unsigned)i < (unsigned)m && idx0[i] == t;                   // (:271)
       // mutual1 implies mutual0 at i, so mscores0[i] = exp(max0[i])                   (:274)
       ms = mutual ? expf(max0[i]) : 0.f;
       if (mutual && ms > a.threshold) mi = i;                                          // (:276,278)

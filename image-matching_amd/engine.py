@@ -79,6 +79,8 @@ class Engine:
         for i, name in enumerate(layers):
             cfg.gnn_layer_is_cross[i] = 1 if name == "cross" else 0
         kenc = [int(c) for c in sg["keypoint_encoder"]]
+        if not 1 <= len(kenc) <= L.IMX_MAX_KENC:
+            raise ImxError(f"keypoint_encoder needs 1 to {L.IMX_MAX_KENC} entries, got {len(kenc)}")
         cfg.kenc_n = len(kenc)
         for i, c in enumerate(kenc):
             cfg.kenc_channels[i] = c

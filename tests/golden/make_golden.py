@@ -719,8 +719,55 @@ def strict_ties():
     npz("strict_ties.npz", ties=np.array(out, np.int32).reshape(-1, 12))
 
 
+def sg_layers():
+    """The reference's SuperGlue on GNN layer lists and keypoint encoders other than the shipped ones (tests/sg_shapes.py names them),
+    built through build_sg(layers=...) with the "t" weight set, on sg_small's inputs (d = 128, 120 x 160).  Writes
+    tests/golden/sg_layers.npz: per net the match indices, the matching scores and strided samples of every layer's output, of
+    scores_in and of Z -- fp32, and the float64 evaluation of the same module as float32 differences (as strict_c3.npz does).  The
+    oracle is held to these (tests/test_sg_shapes_host.py)."""
+    import copy
+    from tests import sg_shapes
+    g = dict(np.load(os.path.join(OUT, "sg_small.npz")))
+    d, (kenc, iters, thr) = 128, synth.SG_CONFIGS[128]
+    x = torch.zeros(1, 1, 120, 160)
+    data = {"image0": x, "image1": x, **{k: torch.from_numpy(g[k]) for k in sg_shapes.KEYS}}
+    sk, sc, ss = sg_shapes.GOLDEN_STRIDE_K, sg_shapes.GOLDEN_STRIDE_C, sg_shapes.GOLDEN_STRIDE_S
+    arrs = {}
+    for lname, ename in sg_shapes.GOLDEN_NETS:
+        layers, enc = sg_shapes.LISTS[lname], sg_shapes.ENCODERS[ename] if ename else kenc
+        sg, _ = build_sg(d, enc, iters, thr, layers=list(layers), gains=synth.SGT_GAINS[d])
+        assert sg.gnn.names == list(layers) and len(sg.gnn.layers) == len(layers)
+        sg.load_state_dict(to_torch(synth.make_superglue_state_dict(d, enc, len(layers), variant="t")))
+        sg.eval()
+        r, dn = sg(data), sg_dense(sg, data)
+        sg64 = copy.deepcopy(sg).double()
+        dn64 = sg_dense(sg64, {k: v.double() for k, v in data.items()})
+        tag = lname + ("_" + ename if ename else "")
+
+        def samples(x):
+            out = {"kenc": torch.stack([x["kenc0"][0, ::sc, ::sk], x["kenc1"][0, ::sc, ::sk]]),
+                   "scores_in": x["scores_in"][0, ::ss, ::ss], "Z": x["Z"][0, ::ss, ::ss]}
+            if layers:
+                out["gnn"] = torch.stack([torch.stack([x["taps"][l][0][0, ::sc, ::sk], x["taps"][l][1][0, ::sc, ::sk]]) for l in range(len(layers))])
+            return out
+        s32, s64 = samples(dn), samples(dn64)
+        for k in s32:
+            arrs[f"{tag}/{k}"] = s32[k].numpy()
+            arrs[f"{tag}/{k}_d64"] = (s64[k] - s32[k].double()).float().numpy()
+        for k in ("matches0", "matches1", "matching_scores0", "matching_scores1"):
+            arrs[f"{tag}/{k}"] = r[k].numpy()
+        Z64 = dn64["Z"]
+        i0, i1 = Z64[:, :-1, :-1].max(2).indices, Z64[:, :-1, :-1].max(1).indices
+        arrs[f"{tag}/idx0_f64"], arrs[f"{tag}/idx1_f64"] = i0.numpy().astype(np.int32), i1.numpy().astype(np.int32)
+        worst = max(float(((s32[k].double() - s64[k]).abs() / (1e-4 + 1e-4 * s64[k].abs())).max()) for k in s32)
+        print(f"sg_layers {tag}: {len(layers)} layers, encoder {enc}: {int((r['matches0'] > -1).sum())} matches; reference fp32 vs float64 on the samples: {worst:.3f} of the bar", flush=True)
+    npz("sg_layers.npz", **arrs)
+
+
 if __name__ == "__main__":
-    if "--strict-ties" in sys.argv:
+    if "--sg-layers" in sys.argv:
+        sg_layers()
+    elif "--strict-ties" in sys.argv:
         strict_ties()
     elif "--heavy-check" in sys.argv:
         heavy_check()
